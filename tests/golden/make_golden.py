@@ -20,6 +20,13 @@ and the layer is discontinuous in it), and the reference's outputs:
   grad_feat1 / grad_feat2     : autograd of sum(out * grad_out)
 Semantics recorded in each file: align_corners=False (default of the torch in
 this image, 2.10), USE_CORRECT_NORMALIZE as per case.
+Optional per case: `image_resize` / `predict_resize` (DATASETS.IMAGE_RESIZE /
+PREDICT_RESIZE; stored as the keys of the same names, a file without them means
+1.0; the synthetic cameras project into the scaled image of image x image_resize
+x predict_resize pixels, DATASETS.IMAGE_SIZE stays 4H) and `softmax_scale`
+(EPIPOLAR.SOFTMAXSCALE; always stored as `softmax_scale`).
+The cases added for the geometry settings stay within 1 MiB each: one pair at
+10 x 10 for the 256-channel head, a three-row subset at 64 x 64.
 """
 import os
 import sys
@@ -62,6 +69,15 @@ CASES = [
     dict(name="rig_nearrect_x_64x64_c8_k64", rig="near_rectified_x", H=64, C=8, K=64, frames=1, image=256, jitter=None, relu=True, correct=True, softmax=True, pairs=1, rows=(0, 13, 31, 32, 33, 50, 63)),
     dict(name="rig_nearrect_y_64x64_c8_k64", rig="near_rectified_y", H=64, C=8, K=64, frames=1, image=256, jitter=None, relu=True, correct=True, softmax=True, pairs=1, rows=(0, 13, 31, 50, 63)),
     dict(name="rig_h36m_64x64_c8_k64", rig="h36m_room", H=64, C=8, K=64, frames=1, image=256, jitter=(0.05, 8.0), relu=True, correct=True, softmax=True, rows=(0, 13, 31, 50, 63)),
+    # ---- the geometry settings real configs use besides the headline one: legacy normalize (the default of core/config.py:118
+    # and of five epipolar YAMLs), resize factors that are not powers of two (IMAGE_RESIZE 1000/256) and the built-in defaults
+    # (IMAGE_RESIZE 2, PREDICT_RESIZE 4), a soft-max scale of 1/sqrt(K); 256 channels, so that the tile kernels run on them
+    dict(name="legacy_10x10_c256_k16", H=10, C=256, K=16, frames=1, image=40, jitter=(0.05, 3.0), relu=True, correct=False, softmax=True, pairs=1),
+    dict(name="legacy_inside_10x10_c256_k16", rig="epipole_inside", H=10, C=256, K=16, frames=1, image=40, jitter=(0.05, 3.0), relu=True, correct=False, softmax=True, pairs=1),
+    dict(name="legacy_64x64_c8_k64", H=64, C=8, K=64, frames=1, image=256, jitter=(0.05, 8.0), relu=True, correct=False, softmax=True, pairs=1, rows=(0, 31, 63)),
+    dict(name="resize3p9_10x10_c256_k16", H=10, C=256, K=16, frames=1, image=40, jitter=(0.05, 3.0), relu=True, correct=True, softmax=True, pairs=1, image_resize=3.90625),
+    dict(name="resize2x4_legacy_10x10_c256_k16", H=10, C=256, K=16, frames=1, image=40, jitter=(0.05, 3.0), relu=True, correct=False, softmax=True, pairs=1, image_resize=2.0, predict_resize=4.0),
+    dict(name="scale_10x10_c256_k33", H=10, C=256, K=33, frames=1, image=40, jitter=(0.05, 3.0), relu=True, correct=True, softmax=True, pairs=1, softmax_scale=33 ** -0.5),
 ]
 
 
@@ -71,12 +87,17 @@ def run_case(c):
           "EPIPOLAR.SAMPLESIZE", str(c["K"]), "DATASETS.IMAGE_SIZE", "(%d, %d)" % (c["image"], c["image"]),
           "EPIPOLAR.USE_CORRECT_NORMALIZE", str(c["correct"]), "EPIPOLAR.SOFTMAX_ENABLED", str(c["softmax"]),
           "VIS.EPIPOLAR_LINE", "True"]
+    ir, pr = float(c.get("image_resize", 1.0)), float(c.get("predict_resize", 1.0))
+    ov += ["DATASETS.IMAGE_RESIZE", repr(ir), "DATASETS.PREDICT_RESIZE", repr(pr)]
+    if "softmax_scale" in c:
+        ov += ["EPIPOLAR.SOFTMAXSCALE", repr(float(c["softmax_scale"]))]
     mod, cfg = rh.reference_epipolar(overrides=ov)
     seed = abs(hash(c["name"])) % 1000 if False else sum(map(ord, c["name"])) % 1000
+    cam_image = c["image"] * ir * pr            # the cameras project into the image the resize factors scale the grid to
     if "rig" in c:
-        P1, P2 = syn.rig_pairs(c["rig"], c["frames"], c["image"], seed=seed, jitter=c["jitter"])
+        P1, P2 = syn.rig_pairs(c["rig"], c["frames"], cam_image, seed=seed, jitter=c["jitter"])
     else:
-        P1, P2 = syn.make_pairs(c["frames"], c.get("views", 4), c["image"], seed=seed, jitter=c["jitter"])
+        P1, P2 = syn.make_pairs(c["frames"], c.get("views", 4), cam_image, seed=seed, jitter=c["jitter"])
     if "pairs" in c:
         P1, P2 = P1[: c["pairs"]], P2[: c["pairs"]]
     if "pair_index" in c:
@@ -133,6 +154,8 @@ def run_case(c):
         downsample=np.float32(cfg.BACKBONE.DOWNSAMPLE),
         torch_version=np.array(torch.__version__),
     )
+    if "image_resize" in c or "predict_resize" in c:
+        data.update(image_resize=np.float32(ir), predict_resize=np.float32(pr))
     return data
 
 

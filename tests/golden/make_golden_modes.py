@@ -25,6 +25,10 @@ CASES = [
     dict(name="param_pool_c16_k16", C=16, K=16, ov=["EPIPOLAR.PARAMETERIZED", "('z', 'theta', 'phi', 'g')",
                                                      "EPIPOLAR.POOLING", "True", "EPIPOLAR.BOTTLENECK", "2",
                                                      "EPIPOLAR.ZRESIDUAL", "False"]),
+    # ... as that YAML runs it: it keeps USE_CORRECT_NORMALIZE at the default False (legacy normalize)
+    dict(name="param_pool_legacy_c16_k16", C=16, K=16, ov=["EPIPOLAR.PARAMETERIZED", "('z', 'theta', 'phi', 'g')",
+                                                            "EPIPOLAR.POOLING", "True", "EPIPOLAR.BOTTLENECK", "2",
+                                                            "EPIPOLAR.ZRESIDUAL", "False", "EPIPOLAR.USE_CORRECT_NORMALIZE", "False"]),
     dict(name="attention_max_c8_k8", C=8, K=8, ov=["EPIPOLAR.ATTENTION", "max", "EPIPOLAR.PARAMETERIZED", "('z',)",
                                                    "EPIPOLAR.ZRESIDUAL", "True"]),
     dict(name="cosine_c8_k8", C=8, K=8, ov=["EPIPOLAR.SIMILARITY", "cos", "EPIPOLAR.PARAMETERIZED", "('z',)",
@@ -48,7 +52,7 @@ CASES = [
 
 def run_case(c):
     ov = ["KEYPOINT.HEATMAP_SIZE", "(%d, %d)" % (H, H), "KEYPOINT.NFEATS", str(c["C"]), "EPIPOLAR.SAMPLESIZE", str(c["K"]),
-          "DATASETS.IMAGE_SIZE", "(%d, %d)" % (IMAGE, IMAGE), "EPIPOLAR.USE_CORRECT_NORMALIZE", "True"] + c["ov"]
+          "DATASETS.IMAGE_SIZE", "(%d, %d)" % (IMAGE, IMAGE), "EPIPOLAR.USE_CORRECT_NORMALIZE", "True"] + c["ov"]   # (a case's own overrides come last and win)
     seed = sum(map(ord, c["name"])) % 1000
     torch.manual_seed(seed)            # (the reference draws its prior tables from the global generator, epipolar.py:79-80)
     mod, cfg = rh.reference_epipolar(overrides=ov)

@@ -105,7 +105,8 @@ def _spec_from_golden(d, **kw):
     m = d["dims"]
     return ops.LayerSpec(H=m["H"], W=m["W"], K=m["K"], downsample=float(d["downsample"]),
                          correct_normalize=m["correct"], softmax_scale=float(d["softmax_scale"]),
-                         softmax_enabled=m["softmax"], **kw)
+                         softmax_enabled=m["softmax"], image_resize=float(d.get("image_resize", 1.0)),
+                         predict_resize=float(d.get("predict_resize", 1.0)), **kw)
 
 
 @pytest.mark.parametrize("case", golden_cases())

@@ -36,7 +36,7 @@ def _module(d):
                          # the fixtures start from configs/epipolar/keypoint_h36m_zresidual_fixed.yaml (:27-35) ...
                          "EPIPOLAR.ATTENTION", "avg", "EPIPOLAR.PARAMETERIZED", ("z",), "EPIPOLAR.ZRESIDUAL", True,
                          "EPIPOLAR.MERGE", "late", "EPIPOLAR.SHARE_WEIGHTS", True] +
-                        [str(v) for v in d["overrides"]])     # ... plus the case's own overrides
+                        [str(v) for v in d["overrides"]])     # ... plus the case's own overrides (last: they win, e.g. legacy normalize)
     mod = Epipolar(cfg=cfg).cuda().eval()
     sd = {k[3:]: torch.from_numpy(d[k]) for k in d.files if k.startswith("sd.")}
     assert sorted(mod.state_dict()) == sorted(sd), (sorted(mod.state_dict()), sorted(sd))   # same keys as the reference module
@@ -49,6 +49,11 @@ def _module(d):
     cam = torch.from_numpy(d["cam"]).cuda()
     mod._cams.get = lambda *a, **k: cam                        # the algebra the reference computed for the fixture
     return mod
+
+
+def _correct(mod):
+    """USE_CORRECT_NORMALIZE the module runs with (the de-normalisation of corr_pos depends on it)"""
+    return bool(mod.cfg.EPIPOLAR.USE_CORRECT_NORMALIZE)
 
 
 @pytest.mark.parametrize("name", MODES)
@@ -66,7 +71,7 @@ def test_mode_vs_reference(name):
     # corr_pos may differ from the reference's only where the arg-max has a PROVEN tie in our own similarity (`depth`)
     locs = ops.sample_locs(mod.layer_spec(), torch.from_numpy(d["cam"]).cuda()).cpu().numpy()      # (K,N,H,W,2)
     got_corr, depth_np = corr.cpu().numpy(), depth.detach().cpu().numpy()
-    ties = assert_corr_pos(locs, got_corr, d["corr_pos"], depth_np, True, tie=2e-6, max_frac=2e-2)   # (N,H,W) bool
+    ties = assert_corr_pos(locs, got_corr, d["corr_pos"], depth_np, _correct(mod), tie=2e-6, max_frac=2e-2)   # (N,H,W) bool
     assert np.abs(depth_np - d["depth"]).max() <= 1e-5 * max(1.0, float(np.abs(d["depth"]).max()))
     scale = max(1.0, float(np.abs(d["finalout"]).max()))
     err = np.abs(fin.detach().cpu().numpy() - d["finalout"])
@@ -147,7 +152,7 @@ def test_torch_restatement_vs_reference(name):
     err = np.abs(fin.detach().cpu().numpy() - d["finalout"]).max(1)
     from epipolar_transformers_amd import ops
     locs = ops.sample_locs(mod.layer_spec(), torch.from_numpy(d["cam"]).cuda()).cpu().numpy()
-    ties = assert_corr_pos(locs, corr.cpu().numpy(), d["corr_pos"], depth.detach().cpu().numpy(), True, tie=2e-6, max_frac=2e-2)
+    ties = assert_corr_pos(locs, corr.cpu().numpy(), d["corr_pos"], depth.detach().cpu().numpy(), _correct(mod), tie=2e-6, max_frac=2e-2)
     assert (err <= 1e-4 * scale)[~ties].all() if is_max else err.max() <= 1e-4 * scale
     (fin * dev("grad_out")).sum().backward()
     if not is_max:        # (ATTENTION max: the tie bookkeeping of the gradients is test_mode_vs_reference's)
@@ -249,7 +254,7 @@ def test_general_kernel_vs_reference(name):
     assert tuple(fin.shape) == d["finalout"].shape and tuple(depth.shape) == d["depth"].shape
     locs = ops.sample_locs(mod.layer_spec(), torch.from_numpy(d["cam"]).cuda()).cpu().numpy()
     depth_np = depth.cpu().numpy()
-    ties = assert_corr_pos(locs, corr.cpu().numpy(), d["corr_pos"], depth_np, True, tie=2e-6, max_frac=2e-2)
+    ties = assert_corr_pos(locs, corr.cpu().numpy(), d["corr_pos"], depth_np, _correct(mod), tie=2e-6, max_frac=2e-2)
     assert np.abs(depth_np - d["depth"]).max() <= 1e-5 * max(1.0, float(np.abs(d["depth"]).max()))
     err = np.abs(fin.cpu().numpy() - d["finalout"])
     tol = 1e-4 * max(1.0, float(np.abs(d["finalout"]).max()))

@@ -27,11 +27,16 @@ def env():
     return _lib, camera, ops
 
 
+def _resize(d):
+    """DATASETS.IMAGE_RESIZE / PREDICT_RESIZE of a fixture (keys absent: 1.0, tests/golden/make_golden.py)"""
+    return dict(image_resize=float(d.get("image_resize", 1.0)), predict_resize=float(d.get("predict_resize", 1.0)))
+
+
 def _spec(ops, d, **kw):
     m = d["dims"]
     return ops.LayerSpec(H=m["H"], W=m["W"], K=m["K"], downsample=float(d["downsample"]),
                          correct_normalize=m["correct"], softmax_scale=float(d["softmax_scale"]),
-                         softmax_enabled=m["softmax"], **kw)
+                         softmax_enabled=m["softmax"], **_resize(d), **kw)
 
 
 def _dev(a):
@@ -97,7 +102,7 @@ def test_forward_vs_oracle_full_tensors(env, oracle_mod, case):
     m = d["dims"]
     spec_o = oracle_mod.LayerSpec(m["H"], m["W"], m["K"], downsample=float(d["downsample"]),
                                   correct_normalize=m["correct"], softmax_scale=float(d["softmax_scale"]),
-                                  softmax_enabled=m["softmax"])
+                                  softmax_enabled=m["softmax"], **_resize(d))
     want = oracle_mod.forward(spec_o, d["feat1"], d["feat2"], None, None, cam=d["cam"])
     spec, cam, _, _, out, attn, corr = _run_forward(env, d)
     _close(attn, want["attn"], TOL_ATTN)
@@ -175,7 +180,8 @@ def test_module_dropin_eval_and_train(env, case):
                          "EPIPOLAR.SAMPLESIZE", m["K"], "EPIPOLAR.ATTENTION", "avg",
                          "EPIPOLAR.PARAMETERIZED", ("z",), "EPIPOLAR.ZRESIDUAL", True,
                          "EPIPOLAR.USE_CORRECT_NORMALIZE", m["correct"], "EPIPOLAR.SOFTMAX_ENABLED", m["softmax"],
-                         "EPIPOLAR.SOFTMAXSCALE", float(d["softmax_scale"]), "VIS.EPIPOLAR_LINE", True])
+                         "EPIPOLAR.SOFTMAXSCALE", float(d["softmax_scale"]), "VIS.EPIPOLAR_LINE", True,
+                         "DATASETS.IMAGE_RESIZE", _resize(d)["image_resize"], "DATASETS.PREDICT_RESIZE", _resize(d)["predict_resize"]])
     mod = Epipolar(cfg=cfg).cuda()
     assert sorted(mod.state_dict()) == sorted(["z.weight", "z.bias", "bn.weight", "bn.bias", "bn.running_mean",
                                                "bn.running_var", "bn.num_batches_tracked"])
@@ -197,7 +203,7 @@ def test_module_dropin_eval_and_train(env, case):
         from oracle import oracle as orc
 
         so = orc.LayerSpec(m["H"], m["W"], m["K"], downsample=float(d["downsample"]), correct_normalize=m["correct"],
-                           softmax_scale=float(d["softmax_scale"]), softmax_enabled=m["softmax"])
+                           softmax_scale=float(d["softmax_scale"]), softmax_enabled=m["softmax"], **_resize(d))
         w = orc.forward(so, d["feat1"], d["feat2"], P1, P2)
         for key, tr in (("finalout_eval", False), ("finalout_train", True)):
             fin_o, _, rm_o, rv_o = orc.epilogue(w["out"], d["feat1"], d["z_weight"], d["z_bias"], d["bn_weight"], d["bn_bias"],

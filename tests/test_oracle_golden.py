@@ -11,11 +11,16 @@ import torch
 from conftest import assert_corr_pos, golden_cases, load_golden
 
 
+def _resize(d):
+    """DATASETS.IMAGE_RESIZE / PREDICT_RESIZE of a fixture (keys absent: 1.0, make_golden.py)"""
+    return dict(image_resize=float(d.get("image_resize", 1.0)), predict_resize=float(d.get("predict_resize", 1.0)))
+
+
 def _spec(orc, d):
     m = d["dims"]
     return orc.LayerSpec(m["H"], m["W"], m["K"], downsample=float(d["downsample"]),
                          correct_normalize=m["correct"], softmax_scale=float(d["softmax_scale"]),
-                         softmax_enabled=m["softmax"], align_corners=False)
+                         softmax_enabled=m["softmax"], align_corners=False, **_resize(d))
 
 
 @pytest.mark.parametrize("case", golden_cases())
