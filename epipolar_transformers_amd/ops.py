@@ -366,7 +366,15 @@ def _workspace(device, nbytes: int, tag: str = "bwd") -> torch.Tensor:
     thread), grown on demand: all use is stream-ordered on the stream it is keyed by, and two host threads that launch
     on the SAME device and stream (nn.DataParallel replicas pinned to one GPU) get buffers of their own -- the cache is
     the package's only process-wide mutable state (guarded by a lock; entries of threads that have exited are dropped
-    whenever a buffer is created), and no two callers ever write the same entry.  release_workspaces() drops them."""
+    whenever a buffer is created), and no two callers ever write the same entry.  release_workspaces() drops them.
+
+    What the kernels rely on (include/epipolar_amd.h; pinned by tests/test_gpu_workspace_contracts.py and
+    tests/test_gpu_redzones.py): of the "fwd" buffer ONE word must not hold stale bits -- word 1 of its 64-word header, the
+    sticky error word -- which is why a buffer is created zeroed and grows by swapping in a new zeroed tensor, never by
+    clearing.  Header words 0 and 2..9 are cleared by every tile call before it uses them, everything behind the header is
+    written before it is read, so the forward, the one-kernel layer and the tiled backward of any shape may follow each other
+    on one buffer; the "bwd" / "zstats" / "zbwd" / "zwgrad" buffers may hold anything.  The base need not be 256-byte aligned
+    (the library rounds it up and the sizes include the 256 bytes), and no kernel writes outside the bytes it was given."""
     dev = torch.device(device)
     key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(),
            torch.cuda.current_stream(dev).cuda_stream, tag, threading.get_ident())
@@ -377,6 +385,15 @@ def _workspace(device, nbytes: int, tag: str = "bwd") -> torch.Tensor:
             # zero-initialised ONCE (include/epipolar_amd.h): the tile forward keeps a sticky error word in it
             _workspaces[key] = buf = torch.zeros(nbytes, dtype=torch.uint8, device=device)
     return buf
+
+
+def _own_workspace(workspace, nbytes: int, device, tag: str):
+    """The caller-owned workspace, checked -- or, when the caller gave none, the cached buffer of `tag`."""
+    if workspace is None:
+        return _workspace(device, nbytes, tag)
+    if workspace.dtype != torch.uint8 or workspace.device != device or not workspace.is_contiguous() or workspace.numel() < nbytes:
+        raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, device))
+    return workspace
 
 
 _TILE_ERROR_OFFSET = 4      # bytes: word 1 of the workspace header (et_epipolar_forward_workspace_error_offset: shape-independent)
@@ -498,7 +515,7 @@ def tile_stats(spec: LayerSpec, n: int, c: int, workspace: torch.Tensor) -> torc
 _BWD_EXPLICIT = _lib.ET_VARIANT_BWD_ATOMIC | _lib.ET_VARIANT_BWD_UNSORTED | _lib.ET_VARIANT_NO_TILE
 
 
-def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, form=None, attn=None):
+def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, form=None, attn=None, workspace=None):
     """d(feat_ref), d(feat_src) of forward_nhwc.  Three forms of the same gradient:
       "tile"    MFMA tile formulation, d(feat_src) accumulated with float atomics across tiles: fastest,
                 reproducible to rounding only (C == 256, K <= 256);
@@ -506,7 +523,9 @@ def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, 
       "atomic"  bilinear-transpose scatter with float atomics (no workspace).
     form=None picks "tile" where it applies (unless the spec's variant names a backward form or NO_TILE), else
     "gather"; use_workspace=False means "atomic".  `attn`: the attention forward_nhwc returned for the same inputs
-    (N,K,H,W) -- the tile form then does not recompute the soft-max (one GEMM of five less); the other forms ignore it."""
+    (N,K,H,W) -- the tile form then does not recompute the soft-max (one GEMM of five less); the other forms ignore it.
+    `workspace`: a caller-owned uint8 tensor for the "tile" / "gather" form instead of the cached one (the tile form's has
+    the forward's layout and size: tile_workspace)."""
     n, h, w, c = ref.shape
     xs, ys, steps = spec.constants(ref.device)
     grad_out = grad_out.contiguous()
@@ -528,7 +547,7 @@ def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, 
         if form == "tile":
             if tile_bytes == 0:
                 raise _lib.EpipolarAmdError("the tiled backward needs the 256-channel head (got C=%d, K=%d, %dx%d)" % (c, spec.K, h, w))
-            ws = _workspace(ref.device, tile_bytes, "fwd")
+            ws = _own_workspace(workspace, tile_bytes, ref.device, "fwd")
             _last_tile_backward_ws[(ref.device.index, torch.cuda.current_stream(ref.device).cuda_stream)] = weakref.ref(ws)
             if attn is not None:
                 assert attn.is_cuda and attn.dtype == torch.float32 and tuple(attn.shape) == (n, spec.K, h, w) and attn.is_contiguous()
@@ -538,7 +557,7 @@ def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, 
             ws, ws_bytes = None, 0
             if form == "gather":
                 ws_bytes = int(lib.et_epipolar_backward_workspace_bytes(ctypes.byref(d)))
-                ws = _workspace(ref.device, ws_bytes)
+                ws = _own_workspace(workspace, ws_bytes, ref.device, "bwd")
             _lib.check(lib.et_epipolar_backward(*args, _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(ref)),
                        "et_epipolar_backward")
     return g_ref, g_src
@@ -629,9 +648,10 @@ def residual_gemm(out: torch.Tensor, packed: torch.Tensor, bias: torch.Tensor, f
     return x
 
 
-def z_batch_stats(out: torch.Tensor, packed_wz: torch.Tensor, z_bias: torch.Tensor):
+def z_batch_stats(out: torch.Tensor, packed_wz: torch.Tensor, z_bias: torch.Tensor, workspace: torch.Tensor = None):
     """First pass of the training-mode epilogue (et_z_batch_stats): y = out @ Wz^T + z_bias over the last dimension (256)
-    and its per-channel batch mean / biased variance over all rows.  Returns (y, mean, var)."""
+    and its per-channel batch mean / biased variance over all rows.  Returns (y, mean, var).  `workspace`: a caller-owned uint8
+    tensor instead of the cached one (any contents)."""
     _require_gpu(out, "out")
     c = out.shape[-1]
     if c != 256 or not out.is_contiguous():
@@ -647,16 +667,17 @@ def z_batch_stats(out: torch.Tensor, packed_wz: torch.Tensor, z_bias: torch.Tens
     var = _empty((c,), device=out.device)
     with torch.cuda.device(out.device):
         ws_bytes = int(lib.et_z_batch_stats_workspace_bytes(rows))
-        ws = _workspace(out.device, ws_bytes, "zstats")
+        ws = _own_workspace(workspace, ws_bytes, out.device, "zstats")
         _lib.check(lib.et_z_batch_stats(rows, c, _ptr(out), _ptr(packed_wz), _ptr(z_bias), _ptr(y), _ptr(mean), _ptr(var), _ptr(ws),
                                         ctypes.c_size_t(ws_bytes), _stream(out)), "et_z_batch_stats")
     return y, mean, var
 
 
 def z_backward(g: torch.Tensor, y: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor, gamma: torch.Tensor,
-               packed_wzt: torch.Tensor, zresidual: bool):
+               packed_wzt: torch.Tensor, zresidual: bool, workspace: torch.Tensor = None):
     """Backward of the training-mode epilogue w.r.t. `out` and the batch norm's affine parameters (et_z_backward): g, y
-    (..., 256) contiguous.  Returns (grad_out, grad_y, grad_gamma, grad_beta)."""
+    (..., 256) contiguous.  Returns (grad_out, grad_y, grad_gamma, grad_beta).  `workspace`: a caller-owned uint8 tensor instead
+    of the cached one (any contents)."""
     _require_gpu(g, "g")
     _require_gpu(y, "y")
     c = g.shape[-1]
@@ -673,16 +694,17 @@ def z_backward(g: torch.Tensor, y: torch.Tensor, mean: torch.Tensor, invstd: tor
     ggamma, gbeta = _empty((c,), device=g.device), _empty((c,), device=g.device)
     with torch.cuda.device(g.device):
         ws_bytes = int(lib.et_z_backward_workspace_bytes(rows))
-        ws = _workspace(g.device, ws_bytes, "zbwd")
+        ws = _own_workspace(workspace, ws_bytes, g.device, "zbwd")
         _lib.check(lib.et_z_backward(rows, c, _ptr(g), _ptr(y), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(packed_wzt),
                                      1 if zresidual else 0, _ptr(gout), _ptr(gy), _ptr(ggamma), _ptr(gbeta), _ptr(ws),
                                      ctypes.c_size_t(ws_bytes), _stream(g)), "et_z_backward")
     return gout, gy, ggamma, gbeta
 
 
-def z_wgrad(grad_y: torch.Tensor, out: torch.Tensor):
+def z_wgrad(grad_y: torch.Tensor, out: torch.Tensor, workspace: torch.Tensor = None):
     """d Wz (256, 256) = grad_y^T @ out and d bz (256) = grad_y.sum(rows) over (..., 256) contiguous tensors (et_z_wgrad:
-    three-term bf16 MFMAs with fp32 accumulation, no atomics, bit-reproducible)."""
+    three-term bf16 MFMAs with fp32 accumulation, no atomics, bit-reproducible).  `workspace`: a caller-owned uint8 tensor
+    instead of the cached one (any contents)."""
     _require_gpu(grad_y, "grad_y")
     _require_gpu(out, "out")
     c = out.shape[-1]
@@ -693,7 +715,7 @@ def z_wgrad(grad_y: torch.Tensor, out: torch.Tensor):
     lib = _lib.load()
     with torch.cuda.device(out.device):
         ws_bytes = int(lib.et_z_wgrad_workspace_bytes(rows))     # (sized by the CU count of the CURRENT device: inside the guard)
-        ws = _workspace(out.device, ws_bytes, "zwgrad")
+        ws = _own_workspace(workspace, ws_bytes, out.device, "zwgrad")
         _lib.check(lib.et_z_wgrad(rows, c, _ptr(grad_y), _ptr(out), _ptr(gw), _ptr(gb), _ptr(ws), ctypes.c_size_t(ws_bytes),
                                   _stream(out)), "et_z_wgrad")
     return gw, gb

@@ -135,8 +135,21 @@ int et_epipolar_forward(const EtLayerDesc *desc, const float *xs, const float *y
  * (EPIPOLAR.SOFTMAX_ENABLED False: the "attention" sim / K is unbounded) and every call with
  * ET_VARIANT_TILE_EXACT.  Same arguments and results as et_epipolar_forward (rounding differs at the
  * 1e-6 level: the sums are re-associated), plus
- *   workspace : device scratch of at least et_epipolar_forward_workspace_bytes(desc) bytes, 256-byte
- *               aligned, ZERO-INITIALISED ONCE by the caller when it is allocated.  It starts with a
+ *   workspace : device scratch of at least et_epipolar_forward_workspace_bytes(desc) bytes.  The base
+ *               need NOT be 256-byte aligned (16 bytes is what the tests exercise and what a caller may
+ *               rely on): the library rounds the base up to the next 256-byte boundary
+ *               itself (the header and every offset below are counted from THERE -- a caller that reads
+ *               the words does the same) and et_epipolar_forward_workspace_bytes includes the 256 bytes
+ *               this can cost; nothing is written outside [base, base + workspace_bytes).
+ *               ZERO-INITIALISED ONCE by the caller when it is allocated, of which the kernels rely on
+ *               ONE word only: word 1 of the header (the sticky error word) must not hold stale bits.
+ *               Header words 0 and 2..9 (the counters of one call) are cleared by every call before it
+ *               uses them, everything behind the header is written by a call before it reads it, and
+ *               header words 10..63 are touched by nothing (reserved: keep them zero).  One workspace
+ *               may therefore serve calls of any shape, variant and direction (et_epipolar_forward_tiled,
+ *               _fused, et_epipolar_backward_tiled(_attn)) in any order, as long as they are ordered on
+ *               one stream and it is large enough for each; concurrent streams need one each
+ *               (tests/test_gpu_workspace_contracts.py pins all of this).  It starts with a
  *               64-word header -- word 0 the overflow-tile count, word 1 a STICKY int32 error word
  *               (et_epipolar_forward_workspace_error_offset(desc) = 4 bytes in, whatever the shape, so
  *               that a workspace reused across shapes keeps ONE error word: the kernels only ever OR

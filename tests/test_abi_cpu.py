@@ -246,3 +246,37 @@ def test_outputs_are_poisoned_under_test():
     assert ops.POISON_OUTPUTS, "tests/conftest.py must switch NaN-poisoning of the output buffers on"
     t = ops._empty((4, 3), device="cpu")
     assert bool(torch.isnan(t).all())
+
+
+def test_tile_workspace_size_functions_are_consistent(lib):
+    """The layout the GPU tests rely on (csrc/et_tile_host.h): the statistics region lies inside the workspace in front of the
+    256 bytes kept for aligning the base, the sticky error word sits 4 bytes in whatever the shape, the tiled backward asks for
+    the forward's size, and sizes do not shrink with N (a workspace sized for the largest batch serves the smaller ones)."""
+    eligible = 0
+    for h, w in ((8, 8), (10, 10), (16, 16), (33, 20), (20, 60), (40, 96), (64, 64), (96, 96), (128, 128), (7, 1)):
+        for k in (2, 16, 33, 64, 100, 128, 256):
+            for variant in (0, _lib.ET_VARIANT_TILE_SPLIT, _lib.ET_VARIANT_TILE_CLASSIC, _lib.ET_VARIANT_WS_BAND):
+                prev = 0
+                for n in (1, 2, 3, 8, 128):
+                    d = ops.LayerSpec(H=h, W=w, K=k, variant=variant).desc(n, 256)
+                    total = int(lib.et_epipolar_forward_workspace_bytes(ctypes.byref(d)))
+                    bwd = int(lib.et_epipolar_backward_tiled_workspace_bytes(ctypes.byref(d)))
+                    assert bwd == total
+                    if total == 0:      # the tile path does not apply: for no N of this shape
+                        assert prev == 0 and int(lib.et_epipolar_forward_workspace_error_offset(ctypes.byref(d))) == 0
+                        continue
+                    eligible += 1
+                    tiles = n * ((h * w + 31) // 32)
+                    stats = int(lib.et_epipolar_forward_workspace_stats_offset(ctypes.byref(d)))
+                    assert stats == 4 * (64 + 32 * tiles + tiles)               # header | perm | overflow list | stats
+                    assert stats + 4 * tiles <= total - 256
+                    assert int(lib.et_epipolar_forward_workspace_error_offset(ctypes.byref(d))) == 4
+                    assert total >= prev and total % 4 == 0
+                    prev = total
+    assert eligible > 300
+    d = ops.LayerSpec(H=16, W=16, K=16).desc(2, 64)                              # not the 256-channel head: no tile path
+    assert int(lib.et_epipolar_forward_workspace_bytes(ctypes.byref(d))) == 0
+    assert int(lib.et_epipolar_backward_tiled_workspace_bytes(ctypes.byref(d))) == 0
+    for fn in (lib.et_z_batch_stats_workspace_bytes, lib.et_z_backward_workspace_bytes):
+        sizes = [int(fn(ctypes.c_int64(r))) for r in (1, 5, 64, 65, 112, 1587, 70000)]
+        assert all(s > 0 for s in sizes) and sizes == sorted(sizes)
