@@ -33,7 +33,8 @@ ET_VARIANT_WS_SETPRIO = 262144
 ET_VARIANT_TILE_EXACT = 524288
 ET_VARIANT_WS_BAND = 1048576
 ET_VARIANT_BWD_SPLIT_IN_PLACE = 2097152
-ET_ABI_VERSION = 13
+ET_VARIANT_BWD_DETERMINISTIC = 4194304
+ET_ABI_VERSION = 14
 ET_GENERAL_POOLING = 1
 ET_GENERAL_PRIOR_MUL = 2
 ET_GENERAL_COSINE = 4
@@ -77,6 +78,9 @@ _SIGNATURES = {
     "et_epipolar_backward_tiled_workspace_bytes": (ctypes.c_size_t, [_D]),
     "et_epipolar_backward_tiled": (ctypes.c_int, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "et_epipolar_backward_tiled_attn": (ctypes.c_int, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "et_epipolar_backward_tiled_det_workspace_bytes": (ctypes.c_size_t, [_D]),
+    "et_epipolar_backward_tiled_det": (ctypes.c_int, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "et_debug_host_det_quantum": (ctypes.c_int, [_D, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P]),
     "et_epipolar_backward_workspace_bytes": (ctypes.c_size_t, [_D]),
     "et_epipolar_backward": (ctypes.c_int, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "et_residual_epilogue": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -24,7 +24,7 @@ UNITS = {
     "et_forward_general.hip": ["et_wave_reduce.h"],
     "et_forward_tile.hip": ["kernels_forward_tile.inc", "kernels_forward_tile_ws.inc", "et_tile_host.h", "et_wave_reduce.h", "et_split_f16.h"],
     "et_backward.hip": ["kernels_sample_table.inc", "kernels_backward.inc"],
-    "et_backward_tile.hip": ["kernels_forward_tile.inc", "kernels_backward_tile.inc", "et_tile_host.h", "et_wave_reduce.h", "et_split_f16.h"],
+    "et_backward_tile.hip": ["kernels_forward_tile.inc", "kernels_backward_tile.inc", "kernels_backward_det.inc", "et_tile_host.h", "et_wave_reduce.h", "et_split_f16.h"],
     "et_misc.hip": ["kernels_misc.inc"],
     "et_residual_gemm.hip": ["kernels_residual_gemm.inc", "et_wave_reduce.h"],
 }

@@ -69,7 +69,7 @@ int et_epipolar_forward(const EtLayerDesc *desc, const float *xs, const float *y
     // variant 0 = the tuned default (measured on MI355X, profiles/): for the 256-channel head with K <= 64
     // four pixels per wave in lockstep; otherwise one pixel per wave, batches of 4 samples, <= 96 VGPRs (5 waves/SIMD),
     // waves of a block interleaved over neighbouring pixels
-    int v = desc->variant & ~(ET_VARIANT_NO_TILE | ET_VARIANT_TILE_SPLIT);
+    int v = desc->variant & ~(ET_VARIANT_NO_TILE | ET_VARIANT_TILE_SPLIT | ET_VARIANT_BWD_DETERMINISTIC);
 #ifdef ET_DEV_ABLATE
     constexpr int kAblateBits = ET_VARIANT_ABLATE_NO_LOADS | ET_VARIANT_ABLATE_ONE_ROW;
 #else

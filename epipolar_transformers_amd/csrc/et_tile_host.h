@@ -68,6 +68,10 @@ bool tile_ws_eligible(const EtLayerDesc *d)
 //   backward: [2] four-group tiles met so far, [3] eight-or-more-group tiles met early (kernels_backward_tile.inc: the merged
 //             kernel splits the first 128 / 32 of a call in place and defers the rest to its second launch), [4] over-capacity
 //             tiles met so far (beyond the first 256 of a call they are deferred without a search)
+//   deterministic backward (et_epipolar_backward_tiled_det): [0] deferred tiles that fit the second launch's kernel whole (listed from
+//             the front of the overflow list), [2] those that do not (listed from its back, eight blocks each); [3], [4] unused --
+//             which tile goes where is a function of the tile alone.  Behind the forward layout, from the next 256-byte boundary:
+//             int64 accumulator[N * HW * 256] | quanta[4 * N] | partial maxima[4 * 32 * N]  (et_backward_tile.hip)
 // The backward REUSES the forward's counter words: safe because every call starts with the ordering kernels on the same stream,
 // which zero them -- a change to either user has to keep that.  Which over-capacity tiles a backward call splits in
 // place and which it defers depends on the order its blocks reach those counters and on blockIdx relative to gridDim: the

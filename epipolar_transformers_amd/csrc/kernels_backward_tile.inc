@@ -64,7 +64,17 @@ struct BwdTileParams {
     int *ovf_list;          // ... and listed here (NULL: split in place, as before)
     const int *tile_list;   // second launch: block b takes tile tile_list[b] while b < *tile_count
     const int *tile_count;
+    // The deterministic instances (DET, kernels_backward_det.inc): d(feat_src) is not added into grad_src with float atomics but,
+    // as 64-bit fixed point under the pair's quantum, into an int64 accumulator with integer atomics -- an order-free sum.
+    long long *det_acc;     // (N, H, W, 256) int64, cleared beside the ordering kernel's sort
+    const float *det_q;     // per pair { q, 1 / q, bound, 0 } (det_quantum_kernel)
+    int *det_err;           // the workspace's sticky error word (bit kDetGuardMask: a contribution beyond the bound)
+    int list_cap;           // merged launch: row capacity of the second launch's kernel (a deferred tile beyond it is shared by
+                            // kDetHardParts blocks there)
 };
+
+constexpr int kDetGuardMask = 1 << 2;   // sticky error word, bit 2: a fixed-point contribution of the deterministic backward was out of range
+constexpr int kDetHardParts = 8;    // blocks of the second launch that share a deferred tile beyond that launch's own capacity
 
 #ifndef ET_BWD_ONE_ROUND_256
 #define ET_BWD_ONE_ROUND_256 1      // (development: 0 = two rounds of atomics in the 256-row one-array kernel, as until round 5)
@@ -90,7 +100,11 @@ constexpr int bwd_blocks_per_group(int rows) { return rows == kTileRowsMergedLar
 // one tile (`vb`: its index, pair-major) by one block -- or, in a short list of deferred tiles, by `nparts` blocks: pixel
 // groups are independent (grad_src is added with atomics, every other output is per pixel), so block `part` takes the
 // `part`-th run of kTilePix / nparts pixels.
-template <int KPL, int ROWS>
+// DET (ET_VARIANT_BWD_DETERMINISTIC, et_epipolar_backward_tiled_det): the same five GEMMs; the U x C results are scaled by the
+// pair's 1 / q (a power of two: exact), rounded to int64 and added with 64-bit integer atomics -- integer addition is
+// associative, so the sum does not depend on the arrival order -- and the way a tile is grouped (which decides how its fp32
+// partial sums are rounded) is a pure function of the tile: no counters, no block indices.
+template <int KPL, int ROWS, bool DET = false>
 __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int vb, const int part = 0, const int nparts = 1)
 {
     // ROWS == kTileRowsMerged / kTileRowsMergedLarge (192 columns: 99.5 % of the 64 x 64 tiles; the rest are split into
@@ -142,6 +156,19 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
     const __amdgpu_buffer_rsrc_t gout = make_rsrc(p.gout + (size_t)n * HW * C, map_bytes);
     const __amdgpu_buffer_rsrc_t gsrc = make_rsrc(p.gsrc + (size_t)n * HW * C, map_bytes);
     const float neg_inf = -__builtin_huge_valf();
+    // DET: the pair's int64 accumulator and 1 / q; a contribution of 2^48 quanta or more (or a NaN) -- impossible under the
+    // bound q is made from (kernels_backward_det.inc) -- is reported in the sticky error word and not added
+    long long *det_pair = nullptr;
+    float det_invq = 0.f;
+    if constexpr (DET) {
+        det_pair = tp.det_acc + (size_t)n * HW * C;
+        det_invq = tp.det_q[n * 4 + 1];
+    }
+    auto det_add = [&](float v, long long *dst) {
+        const float s = v * det_invq;
+        if (fabsf(s) < 0x1p48f) __hip_atomic_fetch_add(dst, __float2ll_rn(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else atomicOr(tp.det_err, kDetGuardMask);
+    };
 
     // ---- geometry, once per tile (as the forward) ----
     if (tid < kTilePix) {
@@ -497,9 +524,17 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
 #else
                     if (u < U) {
 #endif
-                        const int off = s_rows[u] * kRowBytes + (c0 + li) * 4;
-                        __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(acc0[r] * inv, gsrc, off, 0, 0);
-                        __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(acc1[r] * inv, gsrc, off + 128, 0, 0);
+                        if constexpr (DET) {
+                            // fixed point under the pair's quantum: v / q is exact (q a power of two), one rounding to int64;
+                            // a lane covers 8 bytes, a half-wave 256 bytes of the row's accumulator
+                            long long *dst = det_pair + (size_t)s_rows[u] * C + c0 + li;
+                            det_add(acc0[r] * inv, dst);
+                            det_add(acc1[r] * inv, dst + 32);
+                        } else {
+                            const int off = s_rows[u] * kRowBytes + (c0 + li) * 4;
+                            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(acc0[r] * inv, gsrc, off, 0, 0);
+                            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(acc1[r] * inv, gsrc, off + 128, 0, 0);
+                        }
                     }
                 }
             }
@@ -818,6 +853,20 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
         // then run them.
         int ngroups = 2, g_first = 0, g_end = -1;
         bool found = false;     // (ngroups has been settled before the plain search)
+        if constexpr (DET && MERGED) {
+            // Deterministic merged launch: EVERY tile that does not fit whole goes to the second launch -- no counter, no block
+            // index decides.  One that fits that launch's kernel whole (U <= list_cap) is listed from the front (count: header
+            // word 0); a larger one from the back (count: header word 2, cleared by the ordering kernel) and is shared there by
+            // kDetHardParts blocks, each splitting its own pixels by the plain search.  Both are functions of the tile alone; only
+            // the order of the entries varies.  Nothing has been added yet.
+            if (tp.ovf_list) {
+                if (tid == 0) {
+                    if (s_misc[0] <= tp.list_cap) tp.ovf_list[atomicAdd(tp.ovf_count, 1)] = vb;
+                    else tp.ovf_list[tp.b.total_blocks - 1 - atomicAdd(tp.ovf_count + 2, 1)] = vb;
+                }
+                return;
+            }
+        }
         if (nparts > 1) {
             // A tile shared by `nparts` blocks: this one owns the `part`-th run of kTilePix / nparts pixels and splits them only as
             // far as THEIR row sets need (usually not at all: one search pass, one group run -- no block waits for a search over
@@ -836,7 +885,7 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
             g_end = g_first + per;
             found = true;
         }
-        if (MERGED && tp.ovf_list) {     // (MERGED: a compile-time constant -- the other kernels carry none of this)
+        if (!DET && MERGED && tp.ovf_list) {     // (MERGED: a compile-time constant -- the other kernels carry none of this)
             // Merged launch with a second launch behind it (round 5).  Splitting a tile in place is a serial chain of group runs
             // inside one block, and a tile's lines overlap -- half the pixels still touch two thirds to nine tenths of the rows:
             //   * two groups that fit (the ring rig's over-capacity tiles: lines side by side): ~2 x a tile, hidden beside the
@@ -916,17 +965,30 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
 }
 
 // The kernel: one tile per block (the launch covers every tile) ...
-template <int KPL, int ROWS>
+template <int KPL, int ROWS, bool DET = false>
 __global__ __launch_bounds__(256, ((ROWS == kTileRowsSmall || ROWS == kTileRowsMerged) && KPL == 1) ? ET_BWD_MERGED_BLOCKS : 2) void epipolar_bwd_tile_kernel(const BwdTileParams tp)
 {
-    bwd_tile_body<KPL, ROWS>(tp, xcd_remap(blockIdx.x, tp.b.total_blocks));
+    bwd_tile_body<KPL, ROWS, DET>(tp, xcd_remap(blockIdx.x, tp.b.total_blocks));
 }
 
 // ... and its list form, the second launch of a merged call: a few blocks per compute unit walk the list of deferred tiles (a
 // launch of one block per tile that finds the list almost empty costs 0.08 ms in block dispatch alone at Config 2).
-template <int KPL, int ROWS>
+template <int KPL, int ROWS, bool DET = false>
 __global__ __launch_bounds__(256, 2) void epipolar_bwd_tile_list_kernel(const BwdTileParams tp)
 {
+    if constexpr (DET) {
+        // The deterministic form: how many blocks share a tile depends on the tile alone -- kDetHardParts for the tiles listed from
+        // the back (beyond this kernel's capacity: chains of group runs, started first), one for those listed from the front.
+        const int easy = tp.tile_count[0], hard = tp.tile_count[2] * kDetHardParts;
+#pragma unroll 1
+        for (int idx = blockIdx.x; idx < hard + easy; idx += gridDim.x) {
+            const bool h = idx < hard;
+            const int vb = tp.tile_list[h ? tp.b.total_blocks - 1 - idx / kDetHardParts : idx - hard];
+            bwd_tile_body<KPL, ROWS, true>(tp, vb, h ? idx % kDetHardParts : 0, h ? kDetHardParts : 1);
+            __syncthreads();
+        }
+        return;
+    }
     // A short list (the ring's one or two tiles, the room rig's two dozen) is a tail of whole group chains, one block each: eight
     // blocks share a tile then.  A long one (epipole inside the map: thousands) fills the chip as it is.
     const int count = *tp.tile_count;

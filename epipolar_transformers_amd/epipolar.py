@@ -27,7 +27,7 @@ import torch
 from torch import nn
 import torch.nn.functional as F
 
-from . import ops
+from . import _lib, ops
 from .camera import PairAlgebraCache
 from .config import amd_knob, get_cfg
 
@@ -199,7 +199,7 @@ class Epipolar(nn.Module):
                float(cfg.DATASETS.IMAGE_RESIZE), float(cfg.DATASETS.PREDICT_RESIZE),
                bool(cfg.EPIPOLAR.USE_CORRECT_NORMALIZE), bool(amd_knob(cfg, "ALIGN_CORNERS", False)),
                float(cfg.EPIPOLAR.SOFTMAXSCALE), bool(cfg.EPIPOLAR.SOFTMAX_ENABLED), mask,
-               int(amd_knob(cfg, "VARIANT", 0)))
+               int(amd_knob(cfg, "VARIANT", 0)) | (_lib.ET_VARIANT_BWD_DETERMINISTIC if bool(amd_knob(cfg, "DETERMINISTIC", False)) else 0))
         if self._spec is None or self._spec[0] != key:
             spec = ops.LayerSpec(H=key[0], W=key[1], K=key[2], downsample=key[3], image_resize=key[4],
                                  predict_resize=key[5], correct_normalize=key[6], align_corners=key[7],

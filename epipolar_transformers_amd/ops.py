@@ -64,7 +64,9 @@ class LayerSpec:
             predict_resize=float(self.predict_resize), correct_normalize=int(self.correct_normalize),
             align_corners=int(self.align_corners), softmax_scale=float(self.softmax_scale),
             softmax_enabled=int(self.softmax_enabled), src_grad_mask=int(self.src_grad_mask),
-            variant=int(self.variant))
+            # (ET_VARIANT_BWD_DETERMINISTIC is read HERE, by backward_nhwc's choice of form; the kernels never see it, so the
+            #  forward of a deterministic layer is the default forward)
+            variant=int(self.variant) & ~_lib.ET_VARIANT_BWD_DETERMINISTIC)
 
 
 def _require_gpu(t: torch.Tensor, name: str):
@@ -230,6 +232,11 @@ class GeneralAttend(torch.autograd.Function):
     def backward(ctx, grad_out, _ga, _gc):
         qn, m1, m2, cam = ctx.saved_tensors[:4]
         pr = ctx.saved_tensors[4] if ctx.has_prior else None
+        if (ctx.spec.variant & _lib.ET_VARIANT_BWD_DETERMINISTIC) and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+            raise RuntimeError("EPIPOLAR_AMD.DETERMINISTIC: the option branches (theta / phi / g, POOLING, PRIOR, cosine, ATTENTION max, "
+                               "supplied depth) accumulate the gradient of a sampled map with float atomics "
+                               "(et_epipolar_backward_general), which is not bit-reproducible; only the headline mode has a "
+                               "deterministic backward")
         gq, gs, gv, gp = backward_general_nhwc(ctx.spec, qn, m1, m2, cam, to_nhwc(grad_out), need_sim=ctx.needs_input_grad[1],
                                                need_val=ctx.needs_input_grad[2], prior=pr,
                                                need_prior=ctx.has_prior and ctx.needs_input_grad[6], **ctx.mode)
@@ -293,7 +300,7 @@ def forward_nhwc(spec: LayerSpec, ref: torch.Tensor, src: torch.Tensor, cam: tor
 def fused_layer_applies(spec: LayerSpec, c: int, n: int = 1) -> bool:
     """True when et_epipolar_forward_fused covers this shape (the warp-specialised tile kernel: C == 256, maps up to
     96 x 96, K <= 64, soft-max on, no variant bit that leaves that kernel)."""
-    allowed = _lib.ET_VARIANT_TILE_SPLIT | _lib.ET_VARIANT_WS_SETPRIO | _lib.ET_VARIANT_WS_BAND
+    allowed = _lib.ET_VARIANT_TILE_SPLIT | _lib.ET_VARIANT_WS_SETPRIO | _lib.ET_VARIANT_WS_BAND | _lib.ET_VARIANT_BWD_DETERMINISTIC
     if not (c == 256 and 2 <= spec.W <= 96 and spec.H <= 96 and spec.K <= 64 and spec.softmax_enabled and
             (spec.variant & ~allowed) == 0):
         return False
@@ -404,8 +411,10 @@ def _read_tile_error(buf: torch.Tensor) -> int:
     return int(buf[base + _TILE_ERROR_OFFSET: base + _TILE_ERROR_OFFSET + 4].view(torch.int32).item())
 
 
-_TILE_ERROR_TEXT = ("the tile forward reported device-side error bits 0x%x (bit 1: a matrix wave of et_epipolar_forward_fused gave "
-                    "up at the barrier in front of its third GEMM; the results of that call are invalid)")
+_TILE_ERROR_TEXT = ("the tile kernels reported device-side error bits 0x%x (bit 1: a matrix wave of et_epipolar_forward_fused gave "
+                    "up at the barrier in front of its third GEMM; bit 2: the deterministic tiled backward met a d(feat_src) "
+                    "contribution beyond its fixed-point range -- the guard behind the quantum's bound, e.g. non-finite inputs -- and "
+                    "did not add it; the results of that call are invalid)")
 
 
 def _clear_tile_error(buf: torch.Tensor):
@@ -515,14 +524,25 @@ def tile_stats(spec: LayerSpec, n: int, c: int, workspace: torch.Tensor) -> torc
 _BWD_EXPLICIT = _lib.ET_VARIANT_BWD_ATOMIC | _lib.ET_VARIANT_BWD_UNSORTED | _lib.ET_VARIANT_NO_TILE
 
 
+def det_tile_workspace(spec: LayerSpec, n: int, c: int, device) -> torch.Tensor:
+    """A caller-owned workspace for backward_nhwc(..., form="tile_det", workspace=...): the forward-layout workspace followed by
+    the int64 accumulator (empty tensor if the tile path does not apply)."""
+    d = spec.desc(n, c)
+    return torch.zeros(int(_lib.load().et_epipolar_backward_tiled_det_workspace_bytes(ctypes.byref(d))), dtype=torch.uint8,
+                       device=device)
+
+
 def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, form=None, attn=None, workspace=None):
-    """d(feat_ref), d(feat_src) of forward_nhwc.  Three forms of the same gradient:
+    """d(feat_ref), d(feat_src) of forward_nhwc.  Four forms of the same gradient:
       "tile"    MFMA tile formulation, d(feat_src) accumulated with float atomics across tiles: fastest,
                 reproducible to rounding only (C == 256, K <= 256);
+      "tile_det" the same tiles, d(feat_src) accumulated as 64-bit fixed point with integer atomics under a per-pair quantum
+                and a tile partition that depends on the inputs only: BIT-REPRODUCIBLE, batch-independent (soft-max on;
+                workspace: det_tile_workspace, N H W 256 x 8 bytes beyond the tile form's);
       "gather"  per-(pixel,row) coefficients -> counting sort -> ordered per-row sums: no float atomics, bit-reproducible;
       "atomic"  bilinear-transpose scatter with float atomics (no workspace).
-    form=None picks "tile" where it applies (unless the spec's variant names a backward form or NO_TILE), else
-    "gather"; use_workspace=False means "atomic".  `attn`: the attention forward_nhwc returned for the same inputs
+    form=None picks "tile" where it applies (unless the spec's variant names a backward form or NO_TILE) -- "tile_det" when the
+    variant carries ET_VARIANT_BWD_DETERMINISTIC and the soft-max is on --, else "gather"; use_workspace=False means "atomic".  `attn`: the attention forward_nhwc returned for the same inputs
     (N,K,H,W) -- the tile form then does not recompute the soft-max (one GEMM of five less); the other forms ignore it.
     `workspace`: a caller-owned uint8 tensor for the "tile" / "gather" form instead of the cached one (the tile form's has
     the forward's layout and size: tile_workspace)."""
@@ -539,7 +559,10 @@ def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, 
             form = "atomic"
         else:
             form = "tile" if tile_bytes > 0 and not (d.variant & _BWD_EXPLICIT) else "gather"
-    if form not in ("tile", "gather", "atomic"):
+            if spec.variant & _lib.ET_VARIANT_BWD_DETERMINISTIC:
+                # prefer the deterministic tile form; where it does not apply "gather" is the (bit-reproducible) choice
+                form = "tile_det" if form == "tile" and spec.softmax_enabled else "gather"
+    if form not in ("tile", "tile_det", "gather", "atomic"):
         raise ValueError("unknown backward form %r" % (form,))
     args = (ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(ref), _ptr(src), _ptr(grad_out),
             _ptr(g_ref), _ptr(g_src))
@@ -553,6 +576,18 @@ def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, 
                 assert attn.is_cuda and attn.dtype == torch.float32 and tuple(attn.shape) == (n, spec.K, h, w) and attn.is_contiguous()
             _lib.check(lib.et_epipolar_backward_tiled_attn(*args[:7], _ptr(attn), *args[7:], _ptr(ws), ctypes.c_size_t(tile_bytes),
                                                            _stream(ref)), "et_epipolar_backward_tiled_attn")
+        elif form == "tile_det":
+            det_bytes = int(lib.et_epipolar_backward_tiled_det_workspace_bytes(ctypes.byref(d)))
+            if det_bytes == 0:
+                raise _lib.EpipolarAmdError("the tiled backward needs the 256-channel head (got C=%d, K=%d, %dx%d)" % (c, spec.K, h, w))
+            ws = _own_workspace(workspace, det_bytes, ref.device, "fwd")
+            _last_tile_backward_ws[(ref.device.index, torch.cuda.current_stream(ref.device).cuda_stream)] = weakref.ref(ws)
+            if attn is not None:
+                assert attn.is_cuda and attn.dtype == torch.float32 and tuple(attn.shape) == (n, spec.K, h, w) and attn.is_contiguous()
+            _lib.check(lib.et_epipolar_backward_tiled_det(*args[:7], _ptr(attn), *args[7:], _ptr(ws), ctypes.c_size_t(ws.numel()),
+                                                          _stream(ref)), "et_epipolar_backward_tiled_det")
+            if POISON_OUTPUTS:          # (test suite: the guard bit surfaces at the call that set it)
+                check_tile_errors(workspace=ws)
         else:
             ws, ws_bytes = None, 0
             if form == "gather":
@@ -743,7 +778,8 @@ class EpipolarAttend(torch.autograd.Function):
     Inputs/outputs are logical NCHW; attn and corr_pos are returned without
     gradient (the reference never back-propagates through them in the
     configurations of BASELINE.json).  The backward takes backward_nhwc's default form: the MFMA tile kernel for
-    the 256-channel head (float atomics across tiles, reproducible to rounding), the bit-reproducible gather form
+    the 256-channel head (float atomics across tiles, reproducible to rounding; with ET_VARIANT_BWD_DETERMINISTIC in the spec's
+    variant -- EPIPOLAR_AMD.DETERMINISTIC -- its bit-reproducible integer-sum form), the bit-reproducible gather form
     otherwise or when the spec's variant carries ET_VARIANT_NO_TILE."""
 
     @staticmethod

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define ET_ABI_VERSION 13
+#define ET_ABI_VERSION 14
 
 /* Static description of one layer call: the cfg keys the reference reads in
  * Epipolar.__init__ (epipolar.py:12-54) and at call time (epipolar.py:303-311,
@@ -84,6 +84,7 @@ typedef struct EtLayerDesc {
 #define ET_VARIANT_WS_BAND 1048576 /* et_epipolar_forward_tiled / _fused, testing: the persistent kernel's instance for maps above 64 x 64 (288-row arrays, slot table over the tile's band) also for smaller maps */
 #define ET_VARIANT_TILE_EXACT 524288 /* et_epipolar_forward_tiled, one-block-per-tile kernel: both GEMMs in exact fp32 (v_mfma_f32_32x32x2_f32) instead of split-fp16 products */
 #define ET_VARIANT_BWD_SPLIT_IN_PLACE 2097152 /* et_epipolar_backward_tiled: split EVERY tile beyond the merged kernel's columns in place (rounds 2-4) instead of deferring the hard ones (those whose group chain would outlast the launch) to a second launch of the one-array kernel: equal to 3.5 % faster on the ring rig, 1.5-2 x slower on geometries with many such tiles */
+#define ET_VARIANT_BWD_DETERMINISTIC 4194304 /* host wrappers / the Python binding: prefer the deterministic tile backward (et_epipolar_backward_tiled_det) where the tile path applies; the kernels never look at it */
 #define ET_VARIANT_BASELINE 256    /* batches of 8, compiler-chosen registers, pixels 4w..4w+3 per wave   */
 /* Bits 64 and 128 are reserved: in development builds of the library (-DET_DEV_ABLATE) they switch the per-pixel
  * kernel's tap loads off for roofline ablations (wrong results by construction); a product build rejects them. */
@@ -257,6 +258,31 @@ int et_epipolar_backward_tiled_attn(const EtLayerDesc *desc, const float *xs, co
                                     const float *cam, const float *feat_ref, const float *feat_src,
                                     const float *attn, const float *grad_out, float *grad_ref, float *grad_src,
                                     void *workspace, size_t workspace_bytes, void *stream);
+
+/* The tiled backward, BIT-REPRODUCIBLE (ABI 14): the same tiles and GEMMs, but the U x C results are not added into grad_src with
+ * float atomics.  Each is scaled by 1 / q -- q one power of two per pair, derived from a BOUND on a contribution,
+ *     32 (2 |softmax_scale| 256 M_g M_src M_ref + M_g) (1 + 1/64),   M_* = max |.| of the pair's grad_out / feat_src / feat_ref,
+ *     q = 2^(floor(log2 bound) + 1 + 14 - 62), at least 2^-100
+ * -- rounded to int64 and added with 64-bit integer atomics into an accumulator in the workspace: integer sums do not depend on
+ * the order.  A last pass writes grad_src = (float)acc * q (one rounding per element).  How a tile is grouped is a pure function
+ * of the tile (every tile beyond the merged kernel's columns goes to the second launch; no counters, no block indices), so the
+ * gradients of a pair are the same bits run after run, on any stream, alone or anywhere in a batch.  grad_ref is per pixel.
+ *   attn      : nullable, as et_epipolar_backward_tiled_attn
+ *   workspace : et_epipolar_backward_tiled_det_workspace_bytes(desc) bytes (0 exactly where the tiled form's is 0): the
+ *               forward-layout workspace -- same 64-word header, same rules (zero-initialised once; any base alignment; may be
+ *               shared with the other tile calls on one stream) -- followed by the int64 accumulator (N H W 256 x 8 bytes), the
+ *               pairs' quanta and maxima, all written before they are read.  Sticky error word, bit 2 (value 4): a contribution
+ *               of 2^48 quanta or more (or a NaN / inf) was met and NOT added -- impossible for finite inputs under the bound;
+ *               the results of that call are invalid.
+ * Fails (et_last_error) with the soft-max off (the "attention" sim / K has no bound: et_epipolar_backward with a workspace is the
+ * bit-reproducible form there), on a workspace that is too small, and where the tile path does not apply.
+ * et_debug_host_det_quantum: HOST test hook, no GPU -- q and the bound for given maxima (desc: softmax_scale). */
+size_t et_epipolar_backward_tiled_det_workspace_bytes(const EtLayerDesc *desc);
+int et_epipolar_backward_tiled_det(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                                   const float *cam, const float *feat_ref, const float *feat_src,
+                                   const float *attn, const float *grad_out, float *grad_ref, float *grad_src,
+                                   void *workspace, size_t workspace_bytes, void *stream);
+int et_debug_host_det_quantum(const EtLayerDesc *desc, float m_ref, float m_src, float m_g, float *q, float *bound);
 
 /* Residual fusion epilogue: x = feat + out + (y * scale[c] + shift[c])
  *   (epipolar.py:250-253 with ZRESIDUAL, then resnet.py:388 `ret + feat`),
