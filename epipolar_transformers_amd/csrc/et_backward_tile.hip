@@ -1,13 +1,14 @@
-// libepipolar_amd.so: the MFMA tile formulation of the backward (et_epipolar_backward_tiled).
+// libepipolar_amd.so: the MFMA tile formulation of the backward (et_epipolar_backward_tiled, _attn, _det).
+// Kernels: the ordering (kernels_tile_order.inc, through et_tile_host.h) and the tile kernel (kernels_backward_tile.inc over
+// kernels_tile_common.inc, the helpers shared with the forward).
 #include <algorithm>
 #include "et_common.h"
+#include "et_tile_host.h"             // the ordering kernels and the host side of a tile call
 
 namespace {
-#include "kernels_forward_tile.inc"   // tile_order_kernel and the tile helpers shared with the forward
-#include "kernels_backward_tile.inc"  // epipolar_bwd_tile_kernel
+#include "kernels_backward_tile.inc"  // epipolar_bwd_tile_kernel / _list_kernel
 #include "kernels_backward_det.inc"   // the deterministic form: maxima, quantum, int64 -> fp32
 }  // namespace
-#include "et_tile_host.h"
 
 namespace {
 // Workspace of the deterministic form: the forward-layout workspace (same header, same sticky error word), then, from the next
@@ -91,28 +92,60 @@ int et_epipolar_backward_tiled_attn(const EtLayerDesc *desc, const float *xs, co
 }  // extern "C"
 
 namespace {
+// One block per tile: (rows, samples per lane, deterministic form) -> the instance.
+template <int KPL, int ROWS>
+int launch_bwd_tile_as(const BwdTileParams &tp, bool det, size_t lds, int dev, hipStream_t st)
+{
+    const unsigned grid = (unsigned)tp.b.total_blocks;
+    return det ? launch_tile_kernel<epipolar_bwd_tile_kernel<KPL, ROWS, true>>("epipolar_bwd_tile_kernel", grid, 256, lds, dev, st, tp)
+               : launch_tile_kernel<epipolar_bwd_tile_kernel<KPL, ROWS, false>>("epipolar_bwd_tile_kernel", grid, 256, lds, dev, st, tp);
+}
+int launch_bwd_tile(const BwdTileParams &tp, int rows, int kpl, bool det, int dev, hipStream_t st)
+{
+    const size_t lds = bwd_tile_lds_bytes(rows, tp.hw_words, kpl);
+    if (rows == kTileRowsMerged) return launch_bwd_tile_as<1, kTileRowsMerged>(tp, det, lds, dev, st);
+    if (rows == kTileRowsMergedLarge) return launch_bwd_tile_as<1, kTileRowsMergedLarge>(tp, det, lds, dev, st);
+    if (rows == kTileRowsSmall)
+        return kpl == 1   ? launch_bwd_tile_as<1, kTileRowsSmall>(tp, det, lds, dev, st)
+               : kpl == 2 ? launch_bwd_tile_as<2, kTileRowsSmall>(tp, det, lds, dev, st)
+                          : launch_bwd_tile_as<4, kTileRowsSmall>(tp, det, lds, dev, st);
+    if (rows == kTileRowsLarge)
+        return kpl == 1   ? launch_bwd_tile_as<1, kTileRowsLarge>(tp, det, lds, dev, st)
+               : kpl == 2 ? launch_bwd_tile_as<2, kTileRowsLarge>(tp, det, lds, dev, st)
+                          : launch_bwd_tile_as<4, kTileRowsLarge>(tp, det, lds, dev, st);
+    return kpl == 2 ? launch_bwd_tile_as<2, kTileRowsHuge>(tp, det, lds, dev, st)      // (512 rows per pixel need K > 96)
+                    : launch_bwd_tile_as<4, kTileRowsHuge>(tp, det, lds, dev, st);
+}
+
+// The second launch of a merged call (K <= 64) over its list of deferred tiles: two blocks per compute unit -- what is
+// resident at once -- walk the list.
+template <int ROWS>
+int launch_bwd_tile_list_as(const BwdTileParams &tp, bool det, int dev, hipStream_t st)
+{
+    const long long total = tp.b.total_blocks, cus = device_cus(dev);
+    const unsigned grid = (unsigned)(total < 2 * cus ? total : 2 * cus);
+    const size_t lds = bwd_tile_lds_bytes(ROWS, tp.hw_words, 1);
+    return det ? launch_tile_kernel<epipolar_bwd_tile_list_kernel<1, ROWS, true>>("epipolar_bwd_tile_list_kernel", grid, 256, lds, dev, st, tp)
+               : launch_tile_kernel<epipolar_bwd_tile_list_kernel<1, ROWS, false>>("epipolar_bwd_tile_list_kernel", grid, 256, lds, dev, st, tp);
+}
+
 int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
                         const float *cam, const float *feat_ref, const float *feat_src, const float *attn,
                         const float *grad_out, float *grad_ref, float *grad_src, void *workspace,
                         size_t workspace_bytes, void *stream)
 {
-    if (int e = validate(desc)) return e;
-    if (!xs || !ys || !steps || !cam || !feat_ref || !feat_src || !grad_out || !grad_ref || !grad_src)
-        return fail("et_epipolar_backward_tiled: NULL pointer");
-    const size_t need = det ? et_epipolar_backward_tiled_det_workspace_bytes(desc) : et_epipolar_backward_tiled_workspace_bytes(desc);
-    if (need == 0)
-        return fail("et_epipolar_backward_tiled: needs C == 256, H*W <= 16384 and 4 min(K, max(W,H)) <= %d "
-                    "(got C=%d H=%d W=%d K=%d); use et_epipolar_backward", tile_rows_cap(desc), desc->C, desc->H,
-                    desc->W, desc->K);
-    if (!workspace || workspace_bytes < need)
-        return fail("et_epipolar_backward_tiled: workspace of %zu bytes is smaller than the %zu required",
-                    workspace ? workspace_bytes : (size_t)0, need);
+    const char *bad_args = (!xs || !ys || !steps || !cam || !feat_ref || !feat_src || !grad_out || !grad_ref || !grad_src) ? "NULL pointer" : nullptr;
+    TileCall c;
+    if (int e = begin_tile_call(desc, "et_epipolar_backward_tiled", bad_args, "et_epipolar_backward",
+                                det ? det_extra_bytes : nullptr, workspace, workspace_bytes, &c))
+        return e;
     if (det && !desc->softmax_enabled)
         return fail("et_epipolar_backward_tiled_det: needs the soft-max (EPIPOLAR.SOFTMAX_ENABLED False makes the attention sim / K, "
                     "-1e10 / K under the mask: no bound to take the fixed-point quantum from); et_epipolar_backward with a workspace "
                     "is the bit-reproducible form there");
     hipStream_t st = (hipStream_t)stream;
-    const int HW = desc->H * desc->W;
+    const int HW = c.HW;
+    const TileWorkspace &w = c.w;
     BwdTileParams tp;
     std::memset(&tp, 0, sizeof(tp));
     BwdParams &p = tp.b;
@@ -120,26 +153,23 @@ int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, cons
     p.xs = xs; p.ys = ys; p.steps = steps; p.cam = cam;
     p.fref = feat_ref; p.fsrc = feat_src; p.gout = grad_out;
     p.gref = grad_ref; p.gsrc = grad_src;
-    tp.tiles_per_pair = (HW + kTilePix - 1) / kTilePix;
-    p.blocks_per_pair = tp.tiles_per_pair;
-    const long long total = (long long)tp.tiles_per_pair * desc->N;
-    if (total > 0x7fffffffLL) return fail("grid too large");
-    p.total_blocks = (int)total;
-    tp.hw_words = (HW + 31) / 32;
-    tp.rows_cap = tile_rows_cap(desc);
+    p.blocks_per_pair = c.tiles_per_pair;
+    p.total_blocks = c.total;
+    tp.tiles_per_pair = c.tiles_per_pair;
+    tp.hw_words = c.hw_words;
+    tp.rows_cap = c.rows_cap;
     tp.attn = attn;
     // (with the per-pair scale estimates of the source maps: the merged kernels run their row-type GEMMs as split-fp16
     //  products; the workspace has the forward's layout.  grad_src is cleared by extra blocks of the ordering kernel: the
     //  tile kernel adds into it)
-    const TileWorkspace w = carve_tile_workspace(workspace, (size_t)total, (size_t)desc->N, (size_t)HW);
     tp.perm = w.perm;
     tp.scales = w.scales;
     // deterministic form: the clearing blocks zero the int64 accumulator instead (twice the bytes); grad_src is written whole by
     // det_finish_kernel
-    const DetWorkspace dw = carve_det_workspace(w, (size_t)total, (size_t)desc->N, (size_t)HW);
+    const DetWorkspace dw = carve_det_workspace(w, (size_t)c.total, (size_t)desc->N, (size_t)HW);
     const size_t clear_vec4 = (size_t)desc->N * HW * (desc->C / 4) * (det ? 2 : 1);     // (C == 256)
     // (header = true: the ordering clears the workspace's overflow counter, which the merged launch below counts into)
-    if (int e = launch_tile_order(desc, xs, ys, cam, feat_ref, feat_src, w, tp.tiles_per_pair, true, w.scales, false,
+    if (int e = launch_tile_order(desc, xs, ys, cam, feat_ref, feat_src, w, c.tiles_per_pair, true, w.scales, false,
                                   det ? reinterpret_cast<float4 *>(dw.acc) : reinterpret_cast<float4 *>(grad_src), clear_vec4, st,
                                   "et_epipolar_backward_tiled(order)"))
         return e;
@@ -164,11 +194,6 @@ int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, cons
                         !(desc->variant & ET_VARIANT_TILE_CLASSIC);
     const int rows = !merged ? tile_rows(desc) : tile_rows(desc) == kTileRowsSmall ? kTileRowsMerged : kTileRowsMergedLarge;
     if (merged && tp.rows_cap > rows) tp.rows_cap = rows;
-    auto lds_of = [&](int r, bool m) {
-        return (size_t)(bwd_tile_array_floats(r) + r + kTilePix + 60 + kTilePix * 4) * 4 + (size_t)tp.hw_words * 8 +
-               ((kpl == 1 && !m) ? (size_t)kTilePix * kWave * 8 : 0);
-    };
-    size_t lds = lds_of(rows, merged);
     // merged launches defer the tiles beyond their columns to a second launch of the one-array kernel (unless the caller tests the
     // splitting: ET_VARIANT_TILE_SPLIT)
     const bool defer = merged && !(desc->variant & (ET_VARIANT_TILE_SPLIT | ET_VARIANT_BWD_SPLIT_IN_PLACE));
@@ -178,68 +203,27 @@ int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, cons
     }
     // capacity of the second launch's kernel: a deferred tile beyond it is shared by kDetHardParts blocks there (deterministic form)
     tp.list_cap = (tile_rows(desc) == kTileRowsSmall && ET_BWD_LIST_MERGED) ? kTileRowsMergedLarge : tile_rows_cap(desc);
-#define ET_BTILE_(KK, RR, DD)                                                                                        \
-    do {                                                                                                             \
-        ET_GRANT_LDS((epipolar_bwd_tile_kernel<KK, RR, DD>), lds, dev);                                              \
-        hipLaunchKernelGGL((epipolar_bwd_tile_kernel<KK, RR, DD>), dim3((unsigned)total), dim3(256), lds, st, tp);   \
-    } while (0)
-#define ET_BTILE(KK, RR)                     \
-    do {                                     \
-        if (det) ET_BTILE_(KK, RR, true);    \
-        else ET_BTILE_(KK, RR, false);       \
-    } while (0)
-#define ET_BLIST_(RR, DD)                                                                                            \
-    do {                                                                                                             \
-        ET_GRANT_LDS((epipolar_bwd_tile_list_kernel<1, RR, DD>), lds, dev);                                          \
-        hipLaunchKernelGGL((epipolar_bwd_tile_list_kernel<1, RR, DD>), dim3(lgrid), dim3(256), lds, st, tp);         \
-    } while (0)
-#define ET_BLIST(RR)                     \
-    do {                                 \
-        if (det) ET_BLIST_(RR, true);    \
-        else ET_BLIST_(RR, false);       \
-    } while (0)
-    if (rows == kTileRowsMerged || rows == kTileRowsMergedLarge) {
-        if (rows == kTileRowsMerged) ET_BTILE(1, kTileRowsMerged);
-        else ET_BTILE(1, kTileRowsMergedLarge);
-        if (defer) {
-            if (int e = check_launch("et_epipolar_backward_tiled(merged)")) return e;
-            tp.tile_list = w.ovf_list;
-            tp.tile_count = w.ovf_count;
-            tp.ovf_list = nullptr;
-            tp.ovf_count = nullptr;
-            tp.rows_cap = tile_rows_cap(desc);
-            lds = lds_of(tile_rows(desc), false);
-            // (two blocks per compute unit -- what is resident at once -- walk the list)
-            const int cus = device_cus(dev);
-            const unsigned lgrid = (unsigned)(total < 2LL * cus ? total : 2LL * cus);
-            if (tile_rows(desc) == kTileRowsSmall && ET_BWD_LIST_MERGED) {
-                // round 6: the deferred tiles of a 64 x 64 map (193 .. ~280 rows) by the MERGED kernel of 288 columns -- one
-                // derivation of the samples' slots for both arrays, no half passes (a tile beyond 288 rows is split there)
-                tp.rows_cap = kTileRowsMergedLarge;
-                lds = lds_of(kTileRowsMergedLarge, true);
-                ET_BLIST(kTileRowsMergedLarge);
-            } else if (tile_rows(desc) == kTileRowsSmall) {
-                ET_BLIST(kTileRowsSmall);
-            } else {
-                ET_BLIST(kTileRowsLarge);
-            }
+    if (int e = launch_bwd_tile(tp, rows, kpl, det, dev, st)) return e;
+    if (defer) {
+        if (int e = check_launch("et_epipolar_backward_tiled(merged)")) return e;
+        tp.tile_list = w.ovf_list;
+        tp.tile_count = w.ovf_count;
+        tp.ovf_list = nullptr;
+        tp.ovf_count = nullptr;
+        tp.rows_cap = tile_rows_cap(desc);
+        int e;
+        if (tile_rows(desc) == kTileRowsSmall && ET_BWD_LIST_MERGED) {
+            // round 6: the deferred tiles of a 64 x 64 map (193 .. ~280 rows) by the MERGED kernel of 288 columns -- one
+            // derivation of the samples' slots for both arrays, no half passes (a tile beyond 288 rows is split there)
+            tp.rows_cap = kTileRowsMergedLarge;
+            e = launch_bwd_tile_list_as<kTileRowsMergedLarge>(tp, det, dev, st);
+        } else if (tile_rows(desc) == kTileRowsSmall) {
+            e = launch_bwd_tile_list_as<kTileRowsSmall>(tp, det, dev, st);
+        } else {
+            e = launch_bwd_tile_list_as<kTileRowsLarge>(tp, det, dev, st);
         }
-    } else if (rows == kTileRowsSmall) {
-        if (kpl == 1) ET_BTILE(1, kTileRowsSmall);
-        else if (kpl == 2) ET_BTILE(2, kTileRowsSmall);
-        else ET_BTILE(4, kTileRowsSmall);
-    } else if (rows == kTileRowsLarge) {
-        if (kpl == 1) ET_BTILE(1, kTileRowsLarge);
-        else if (kpl == 2) ET_BTILE(2, kTileRowsLarge);
-        else ET_BTILE(4, kTileRowsLarge);
-    } else {
-        if (kpl == 2) ET_BTILE(2, kTileRowsHuge);   // (512 rows per pixel need K > 96)
-        else ET_BTILE(4, kTileRowsHuge);
+        if (e) return e;
     }
-#undef ET_BTILE
-#undef ET_BTILE_
-#undef ET_BLIST
-#undef ET_BLIST_
     if (det) {
         if (int e = check_launch("et_epipolar_backward_tiled_det(tiles)")) return e;
         // int64 -> fp32: eight blocks of 256 threads per 64 pixel rows

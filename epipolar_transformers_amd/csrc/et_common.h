@@ -10,6 +10,9 @@
 //   et_backward.hip       kernels_backward.inc       backward, any shape: coefficient emission + scan / bucket / ordered
 //                                                    gather (no float atomics, bit-reproducible), float-atomic fallback
 //   et_backward_tile.hip  kernels_backward_tile.inc  C == 256 head, backward in the same tile form
+//     both tile units:    kernels_tile_order.inc     the ordering of a tile call (sort keys, one bitonic sort per pair)
+//                         kernels_tile_common.inc    device helpers of both directions: taps, array rows, the tile GEMMs
+//                         et_tile_host.h             the host side of a tile call: checks, workspace, ordering, launch
 //   et_misc.hip           kernels_misc.inc           sample_locs, residual epilogue, NCHW <-> NHWC, ABI version / errors
 //   epipolar_geometry.h                              bit-faithful float32 geometry (segment, sample set-up), host+device
 //

@@ -1,13 +1,15 @@
-// libepipolar_amd.so: the MFMA tile formulation of the forward (et_epipolar_forward_tiled).
+// libepipolar_amd.so: the MFMA tile formulation of the forward (et_epipolar_forward_tiled, et_epipolar_forward_fused).
+// Kernels: the ordering (kernels_tile_order.inc, through et_tile_host.h), the persistent warp-specialised kernel
+// (kernels_forward_tile_ws.inc) and the one-block-per-tile kernel (kernels_forward_tile.inc over kernels_tile_common.inc).
 #include "et_common.h"
 #include <cstdlib>
 
-namespace {
-#include "kernels_forward_tile.inc"     // tile_order_kernel, epipolar_fwd_tile_kernel / _list_kernel
-#include "kernels_forward_tile_ws.inc"  // epipolar_fwd_tile_ws_kernel (warp-specialised, persistent): the default
+#include "et_tile_host.h"               // the ordering kernels and the host side of a tile call
 
+namespace {
+#include "kernels_forward_tile.inc"     // epipolar_fwd_tile_kernel / _list_kernel (one block per tile)
+#include "kernels_forward_tile_ws.inc"  // epipolar_fwd_tile_ws_kernel (warp-specialised, persistent): the default
 }  // namespace
-#include "et_tile_host.h"
 
 #ifdef ET_WS_PROFILE
 static long long *g_ws_prof = nullptr;   // profiling builds only (python -m epipolar_transformers_amd.build --profile)
@@ -17,6 +19,129 @@ extern "C" int et_dev_ws_profile(long long *device_buffer)
     return 0;
 }
 #endif
+
+namespace {
+// The parameter block of the one-block-per-tile kernels (its FwdParams are the persistent kernel's too).
+TileParams fwd_tile_params(const EtLayerDesc *desc, const TileCall &c, const float *xs, const float *ys, const float *steps,
+                           const float *cam, const float *feat_ref, const float *feat_src, float *out, float *attn, float *corr_pos)
+{
+    TileParams tp;
+    FwdParams &p = tp.f;
+    p.d = *desc;
+    p.xs = xs; p.ys = ys; p.steps = steps; p.cam = cam;
+    p.fref = feat_ref; p.fsrc = feat_src;
+    p.out = out; p.attn = attn; p.corr = corr_pos;
+    p.res_bias = nullptr; p.res_base = nullptr;
+    p.interleave = 0; p.ablate = 0;
+    p.blocks_per_pair = c.tiles_per_pair;
+    p.total_blocks = c.total;
+    tp.tiles_per_pair = c.tiles_per_pair;
+    tp.hw_words = c.hw_words;
+    tp.rows_cap = c.rows_cap;
+    tp.perm = c.w.perm;
+    tp.stats = c.w.stats;
+    tp.tile_list = c.w.ovf_list;
+    tp.tile_count = c.w.ovf_count;
+    // (per-pair scale estimates of the source maps: for the split-fp16 GEMMs of the persistent kernel and
+    //  of the one-block-per-tile kernel; ET_VARIANT_TILE_EXACT keeps the latter in exact fp32)
+    // soft-max off: exact fp32 throughout, as the header promises (the first GEMM feeds the `== 0 -> -1e10` mask and the
+    // "attention" sim / K is unbounded: no fp16 form of the B rows)
+    tp.scales = ((desc->variant & ET_VARIANT_TILE_EXACT) || !desc->softmax_enabled) ? nullptr : c.w.scales;
+    return tp;
+}
+
+// The persistent kernel's: everything but the fused export's own fields (packed_w, bias, x; there f.out on request only).
+TileWsParams tile_ws_params(const FwdParams &f, const TileCall &c)
+{
+    TileWsParams wp;
+    wp.f = f;
+    wp.perm = c.w.perm;
+    wp.tiles_per_pair = c.tiles_per_pair;
+    wp.total_tiles = c.total;
+    wp.rows_cap = c.rows_cap;
+    wp.ovf_count = c.w.ovf_count;
+    wp.ovf_list = c.w.ovf_list;
+    wp.stats = c.w.stats;
+    wp.scales = c.w.scales;
+    wp.segs = c.w.segs;
+    wp.band = c.w.band;
+    wp.packed_w = nullptr;
+    wp.bias = nullptr;
+    wp.x = nullptr;
+    wp.err = c.w.err;
+    wp.tile_ctr = c.w.ovf_count + 2;
+    wp.setprio = 0;
+    wp.prof = nullptr;
+    return wp;
+}
+
+// The persistent kernel, one block per compute unit.  Instances: 256-row arrays (maps up to 64 x 64); 288-row arrays and a
+// slot table over the tile's band (above 64 x 64, up to 96 x 96); the latter in two passes of 64 samples per tile with an
+// online soft-max (64 < K <= 128, maps up to 128 x 128: sample + attention only, no fused instance).
+template <bool FUSED>
+int launch_fwd_tile_ws(const EtLayerDesc *desc, TileWsParams wp, int dev, hipStream_t st)
+{
+    const int cus = device_cus(dev);
+    const unsigned grid = (unsigned)(wp.total_tiles < cus ? wp.total_tiles : cus), block = (kWsMatrixWaves + 8) * kWave;
+    const bool two_pass = !FUSED && tile_ws_two_pass(desc);
+    if (!two_pass && !tile_ws_band(desc))
+        return launch_tile_kernel<epipolar_fwd_tile_ws_kernel<kTileRowsSmall, 8, FUSED>>(
+            "epipolar_fwd_tile_ws_kernel", grid, block, tile_ws_lds_bytes(kTileRowsSmall, desc->H, desc->W), dev, st, wp);
+    if (wp.rows_cap > kTileRowsWsLarge) wp.rows_cap = kTileRowsWsLarge;
+    const size_t lds = tile_ws_lds_bytes(kTileRowsWsLarge, desc->H, desc->W, true);
+    if constexpr (!FUSED) {
+        if (two_pass)
+            return launch_tile_kernel<epipolar_fwd_tile_ws_kernel<kTileRowsWsLarge, 8, false, true, 2>>("epipolar_fwd_tile_ws_kernel", grid,
+                                                                                                        block, lds, dev, st, wp);
+    }
+    return launch_tile_kernel<epipolar_fwd_tile_ws_kernel<kTileRowsWsLarge, 8, FUSED, true>>("epipolar_fwd_tile_ws_kernel", grid, block,
+                                                                                             lds, dev, st, wp);
+}
+
+// One block per tile: (rows, samples per lane) -> the instance.
+template <int KPL, int ROWS>
+int launch_fwd_tile_as(const TileParams &tp, size_t lds, int dev, hipStream_t st)
+{
+    return launch_tile_kernel<epipolar_fwd_tile_kernel<KPL, ROWS>>("epipolar_fwd_tile_kernel", (unsigned)tp.f.total_blocks, 256, lds,
+                                                                   dev, st, tp);
+}
+int launch_fwd_tile(const TileParams &tp, int rows, int kpl, int dev, hipStream_t st)
+{
+    const size_t lds = fwd_tile_lds_bytes(rows, tp.hw_words, kpl);
+    if (rows == kTileRowsSmall)
+        return kpl == 1   ? launch_fwd_tile_as<1, kTileRowsSmall>(tp, lds, dev, st)
+               : kpl == 2 ? launch_fwd_tile_as<2, kTileRowsSmall>(tp, lds, dev, st)
+                          : launch_fwd_tile_as<4, kTileRowsSmall>(tp, lds, dev, st);
+    if (rows == kTileRowsLarge)
+        return kpl == 1   ? launch_fwd_tile_as<1, kTileRowsLarge>(tp, lds, dev, st)
+               : kpl == 2 ? launch_fwd_tile_as<2, kTileRowsLarge>(tp, lds, dev, st)
+                          : launch_fwd_tile_as<4, kTileRowsLarge>(tp, lds, dev, st);
+    return kpl == 2 ? launch_fwd_tile_as<2, kTileRowsHuge>(tp, lds, dev, st)      // (512 rows per pixel need K > 96)
+                    : launch_fwd_tile_as<4, kTileRowsHuge>(tp, lds, dev, st);
+}
+
+// The tiles the persistent kernel left over, one block per tile: two blocks per compute unit walk the list.
+template <int KPL, int ROWS>
+int launch_fwd_tile_list_as(const TileParams &tp, size_t lds, int dev, hipStream_t st)
+{
+    const long long total = tp.f.total_blocks, cus = device_cus(dev);
+    return launch_tile_kernel<epipolar_fwd_tile_list_kernel<KPL, ROWS>>("epipolar_fwd_tile_list_kernel",
+                                                                        (unsigned)(total < 2 * cus ? total : 2 * cus), 256, lds, dev, st, tp);
+}
+int launch_fwd_tile_list(const TileParams &tp, int rows, int kpl, int dev, hipStream_t st)
+{
+    const size_t lds = fwd_tile_lds_bytes(rows, tp.hw_words, kpl);
+    if (kpl == 2)                   // (the two-pass kernel's left-overs: whole tiles, all K samples, one block per tile)
+        return rows == kTileRowsHuge    ? launch_fwd_tile_list_as<2, kTileRowsHuge>(tp, lds, dev, st)
+               : rows == kTileRowsLarge ? launch_fwd_tile_list_as<2, kTileRowsLarge>(tp, lds, dev, st)
+                                        : launch_fwd_tile_list_as<2, kTileRowsSmall>(tp, lds, dev, st);
+    if (rows == kTileRowsLarge) return launch_fwd_tile_list_as<1, kTileRowsLarge>(tp, lds, dev, st);
+    // (round 6, measured: the left-overs of a map up to 64 x 64 -- all beyond 256 rows -- through the 384-row instance, whole
+    //  instead of in pixel groups, take as long: 136 against 131 us for the near-rectified rig's 640 tiles.  A left-over tile
+    //  is ~65 us of latency in a block either way and the list is two trips of the resident blocks.)
+    return launch_fwd_tile_list_as<1, kTileRowsSmall>(tp, lds, dev, st);
+}
+}  // namespace
 
 extern "C" {
 
@@ -45,144 +170,39 @@ int et_epipolar_forward_tiled(const EtLayerDesc *desc, const float *xs, const fl
                               float *attn, float *corr_pos, const float *res_bias, float *res_base,
                               void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (int e = validate(desc)) return e;
-    if (!xs || !ys || !steps || !cam || !feat_ref || !feat_src || !out)
-        return fail("et_epipolar_forward_tiled: NULL pointer");
-    if (res_bias && !res_base) return fail("et_epipolar_forward_tiled: res_bias given without res_base");
-    if (!tile_eligible(desc))
-        return fail("et_epipolar_forward_tiled: needs C == 256, H*W <= 16384 and 4 min(K, max(W,H)) <= %d "
-                    "(got C=%d H=%d W=%d K=%d); use et_epipolar_forward", tile_rows_cap(desc), desc->C, desc->H, desc->W, desc->K);
-    const size_t need = et_epipolar_forward_workspace_bytes(desc);
-    if (!workspace || workspace_bytes < need)
-        return fail("et_epipolar_forward_tiled: workspace of %zu bytes is smaller than the %zu required",
-                    workspace ? workspace_bytes : (size_t)0, need);
+    const char *bad_args = (!xs || !ys || !steps || !cam || !feat_ref || !feat_src || !out) ? "NULL pointer"
+                           : (res_bias && !res_base)                                        ? "res_bias given without res_base"
+                                                                                            : nullptr;
+    TileCall c;
+    if (int e = begin_tile_call(desc, "et_epipolar_forward_tiled", bad_args, "et_epipolar_forward", nullptr, workspace, workspace_bytes, &c))
+        return e;
     hipStream_t st = (hipStream_t)stream;
-    const int HW = desc->H * desc->W;
-    TileParams tp;
-    FwdParams &p = tp.f;
-    p.d = *desc;
-    p.xs = xs; p.ys = ys; p.steps = steps; p.cam = cam;
-    p.fref = feat_ref; p.fsrc = feat_src;
-    p.out = out; p.attn = attn; p.corr = corr_pos;
-    p.res_bias = res_bias; p.res_base = res_base;
-    p.interleave = 0; p.ablate = 0;
-    tp.tiles_per_pair = (HW + kTilePix - 1) / kTilePix;
-    p.blocks_per_pair = tp.tiles_per_pair;
-    const long long total = (long long)tp.tiles_per_pair * desc->N;
-    if (total > 0x7fffffffLL / kTilePix) return fail("grid too large");
-    p.total_blocks = (int)total;
-    tp.hw_words = (HW + 31) / 32;
-    tp.rows_cap = tile_rows_cap(desc);
-    const TileWorkspace w = carve_tile_workspace(workspace, (size_t)total, (size_t)desc->N, (size_t)HW);
-    tp.perm = w.perm;
-    tp.stats = w.stats;
-    tp.tile_list = w.ovf_list;
-    tp.tile_count = w.ovf_count;
+    TileParams tp = fwd_tile_params(desc, c, xs, ys, steps, cam, feat_ref, feat_src, out, attn, corr_pos);
+    tp.f.res_bias = res_bias;
+    tp.f.res_base = res_base;
     // 1. order every pair's reference pixels by their epipolar line (also clears the overflow counter)
-    const int dev = current_device();
-    // (per-pair scale estimates of the source maps: for the split-fp16 GEMMs of the persistent kernel and
-    //  of the one-block-per-tile kernel; ET_VARIANT_TILE_EXACT keeps the latter in exact fp32)
-    // soft-max off: exact fp32 throughout, as the header promises (the first GEMM feeds the `== 0 -> -1e10` mask and the
-    // "attention" sim / K is unbounded: no fp16 form of the B rows)
-    tp.scales = ((desc->variant & ET_VARIANT_TILE_EXACT) || !desc->softmax_enabled) ? nullptr : w.scales;
-    if (int e = launch_tile_order(desc, xs, ys, cam, feat_ref, feat_src, w, tp.tiles_per_pair, true, w.scales, true, nullptr, 0, st,
+    if (int e = launch_tile_order(desc, xs, ys, cam, feat_ref, feat_src, c.w, c.tiles_per_pair, true, c.w.scales, true, nullptr, 0, st,
                                   "et_epipolar_forward_tiled(order)"))
         return e;
+    const int dev = current_device();
     const int kpl = (desc->K + 63) / 64;
     const int rows = tile_rows(desc);
-    const size_t lds = (size_t)(fwd_tile_array_floats(rows) + rows + kTilePix + 48 + kTilePix * 4) * 4 +
-                       (size_t)tp.hw_words * 8 + (kpl == 1 ? (size_t)kTilePix * kWave * 8 : 0);
-#define ET_SET_LDS(KERNEL, BYTES) ET_GRANT_LDS(KERNEL, BYTES, dev)
-    const bool two_pass = tile_ws_two_pass(desc);
-    if (tile_ws_eligible(desc) || two_pass) {
+    if (tile_ws_eligible(desc) || tile_ws_two_pass(desc)) {
         // 2a. the persistent, warp-specialised kernel (kernels_forward_tile_ws.inc): the default ...
-        TileWsParams wp;
-        wp.f = p;
-        wp.perm = w.perm;
-        wp.tiles_per_pair = tp.tiles_per_pair;
-        wp.total_tiles = (int)total;
-        wp.rows_cap = tp.rows_cap;
-        wp.ovf_count = w.ovf_count;
-        wp.ovf_list = w.ovf_list;
-        wp.stats = w.stats;
-        wp.scales = w.scales;
-        wp.segs = w.segs;
-        wp.band = w.band;
-        wp.packed_w = nullptr;
-        wp.bias = nullptr;
-        wp.x = nullptr;
-        wp.err = w.err;
-        wp.tile_ctr = w.ovf_count + 2;
+        TileWsParams wp = tile_ws_params(tp.f, c);
         wp.setprio = (desc->variant & ET_VARIANT_WS_SETPRIO) ? 1 : 0;
 #ifdef ET_WS_PROFILE
         wp.prof = g_ws_prof;
         if (const char *e = getenv("ET_WS_EXPERIMENT")) wp.setprio |= atoi(e);
-#else
-        wp.prof = nullptr;
 #endif
-        const int cus = device_cus(dev);
-        const unsigned grid = (unsigned)(total < cus ? total : cus);
-        if (two_pass) {                 // 64 < K <= 128: two passes of 64 samples per tile, online soft-max (maps up to 128 x 128)
-            if (wp.rows_cap > kTileRowsWsLarge) wp.rows_cap = kTileRowsWsLarge;
-            const size_t lds_ws = tile_ws_lds_bytes(kTileRowsWsLarge, desc->H, desc->W, true);
-            ET_SET_LDS((epipolar_fwd_tile_ws_kernel<kTileRowsWsLarge, 8, false, true, 2>), lds_ws);
-            hipLaunchKernelGGL((epipolar_fwd_tile_ws_kernel<kTileRowsWsLarge, 8, false, true, 2>), dim3(grid),
-                               dim3((kWsMatrixWaves + 8) * kWave), lds_ws, st, wp);
-        } else if (tile_ws_band(desc)) {       // maps above 64 x 64 (up to 96 x 96): 288-row arrays, slot table over the tile's band
-            if (wp.rows_cap > kTileRowsWsLarge) wp.rows_cap = kTileRowsWsLarge;
-            const size_t lds_ws = tile_ws_lds_bytes(kTileRowsWsLarge, desc->H, desc->W, true);
-            ET_SET_LDS((epipolar_fwd_tile_ws_kernel<kTileRowsWsLarge, 8, false, true>), lds_ws);
-            hipLaunchKernelGGL((epipolar_fwd_tile_ws_kernel<kTileRowsWsLarge, 8, false, true>), dim3(grid),
-                               dim3((kWsMatrixWaves + 8) * kWave), lds_ws, st, wp);
-        } else {
-            const size_t lds_ws = tile_ws_lds_bytes(kTileRowsSmall, desc->H, desc->W);
-            ET_SET_LDS((epipolar_fwd_tile_ws_kernel<kTileRowsSmall, 8>), lds_ws);
-            hipLaunchKernelGGL((epipolar_fwd_tile_ws_kernel<kTileRowsSmall, 8>), dim3(grid), dim3((kWsMatrixWaves + 8) * kWave),
-                               lds_ws, st, wp);
-        }
+        if (int e = launch_fwd_tile_ws<false>(desc, wp, dev, st)) return e;
         if (int e = check_launch("et_epipolar_forward_tiled(ws)")) return e;
         // ... 2b. and the tiles it left over one block per tile
-        const unsigned lgrid = (unsigned)(total < 2LL * cus ? total : 2LL * cus);
-#define ET_LIST(KK, RR)                                                                                                 \
-    do {                                                                                                                \
-        ET_SET_LDS((epipolar_fwd_tile_list_kernel<KK, RR>), lds);                                                       \
-        hipLaunchKernelGGL((epipolar_fwd_tile_list_kernel<KK, RR>), dim3(lgrid), dim3(256), lds, st, tp);               \
-    } while (0)
-        if (kpl == 2) {                 // (the two-pass kernel's left-overs: whole tiles, all K samples, one block per tile)
-            if (rows == kTileRowsHuge) ET_LIST(2, kTileRowsHuge);
-            else if (rows == kTileRowsLarge) ET_LIST(2, kTileRowsLarge);
-            else ET_LIST(2, kTileRowsSmall);
-        } else if (rows == kTileRowsLarge) {
-            ET_LIST(1, kTileRowsLarge);
-        } else {
-            // (round 6, measured: the left-overs of a map up to 64 x 64 -- all beyond 256 rows -- through the 384-row instance, whole
-            //  instead of in pixel groups, take as long: 136 against 131 us for the near-rectified rig's 640 tiles.  A left-over tile
-            //  is ~65 us of latency in a block either way and the list is two trips of the resident blocks.)
-            ET_LIST(1, kTileRowsSmall);
-        }
-#undef ET_LIST
+        if (int e = launch_fwd_tile_list(tp, rows, kpl, dev, st)) return e;
         return check_launch("et_epipolar_forward_tiled(list)");
     }
     // 2. one block per tile
-#define ET_TILE(KK, RR)                                                                                          \
-    do {                                                                                                         \
-        ET_SET_LDS((epipolar_fwd_tile_kernel<KK, RR>), lds);                                                     \
-        hipLaunchKernelGGL((epipolar_fwd_tile_kernel<KK, RR>), dim3((unsigned)total), dim3(256), lds, st, tp);   \
-    } while (0)
-    if (rows == kTileRowsSmall) {
-        if (kpl == 1) ET_TILE(1, kTileRowsSmall);
-        else if (kpl == 2) ET_TILE(2, kTileRowsSmall);
-        else ET_TILE(4, kTileRowsSmall);
-    } else if (rows == kTileRowsLarge) {
-        if (kpl == 1) ET_TILE(1, kTileRowsLarge);
-        else if (kpl == 2) ET_TILE(2, kTileRowsLarge);
-        else ET_TILE(4, kTileRowsLarge);
-    } else {
-        if (kpl == 2) ET_TILE(2, kTileRowsHuge);   // (512 rows per pixel need K > 96)
-        else ET_TILE(4, kTileRowsHuge);
-    }
-#undef ET_TILE
-#undef ET_SET_LDS
+    if (int e = launch_fwd_tile(tp, rows, kpl, dev, st)) return e;
     return check_launch("et_epipolar_forward_tiled");
 }
 
@@ -203,89 +223,29 @@ int et_epipolar_forward_fused(const EtLayerDesc *desc, const float *xs, const fl
         return fail("et_epipolar_forward_fused: needs the warp-specialised tile kernel (C == 256, maps up to 96 x 96, K <= 64, "
                     "soft-max on; got C=%d H=%d W=%d K=%d variant=%d): use et_epipolar_forward_tiled + et_residual_gemm",
                     desc->C, desc->H, desc->W, desc->K, desc->variant);
-    const size_t need = et_epipolar_forward_workspace_bytes(desc);
-    if (!workspace || workspace_bytes < need)
-        return fail("et_epipolar_forward_fused: workspace of %zu bytes is smaller than the %zu required",
-                    workspace ? workspace_bytes : (size_t)0, need);
+    // (its own, narrower eligibility and message above: the descriptor and the shape pass begin_tile_call's checks)
+    TileCall c;
+    if (int e = begin_tile_call(desc, "et_epipolar_forward_fused", nullptr, "et_epipolar_forward_tiled", nullptr, workspace, workspace_bytes, &c))
+        return e;
     hipStream_t st = (hipStream_t)stream;
-    const int HW = desc->H * desc->W;
-    TileParams tp;
-    FwdParams &p = tp.f;
-    p.d = *desc;
-    p.xs = xs; p.ys = ys; p.steps = steps; p.cam = cam;
-    p.fref = feat_ref; p.fsrc = feat_src;
-    p.out = out_scratch; p.attn = attn; p.corr = corr_pos;
-    p.res_bias = nullptr; p.res_base = nullptr;
-    p.interleave = 0; p.ablate = 0;
-    tp.tiles_per_pair = (HW + kTilePix - 1) / kTilePix;
-    p.blocks_per_pair = tp.tiles_per_pair;
-    const long long total = (long long)tp.tiles_per_pair * desc->N;
-    if (total > 0x7fffffffLL / kTilePix) return fail("grid too large");
-    p.total_blocks = (int)total;
-    tp.hw_words = (HW + 31) / 32;
-    tp.rows_cap = tile_rows_cap(desc);
-    const TileWorkspace w = carve_tile_workspace(workspace, (size_t)total, (size_t)desc->N, (size_t)HW);
-    tp.perm = w.perm;
-    tp.stats = w.stats;
-    tp.tile_list = w.ovf_list;
-    tp.tile_count = w.ovf_count;
-    tp.scales = (desc->variant & ET_VARIANT_TILE_EXACT) ? nullptr : w.scales;
-    const int dev = current_device();
-    if (int e = launch_tile_order(desc, xs, ys, cam, feat_ref, feat_src, w, tp.tiles_per_pair, true, w.scales, true, nullptr, 0, st,
+    const TileParams tp = fwd_tile_params(desc, c, xs, ys, steps, cam, feat_ref, feat_src, out_scratch, attn, corr_pos);
+    if (int e = launch_tile_order(desc, xs, ys, cam, feat_ref, feat_src, c.w, c.tiles_per_pair, true, c.w.scales, true, nullptr, 0, st,
                                   "et_epipolar_forward_fused(order)"))
         return e;
-    TileWsParams wp;
-    wp.f = p;
+    const int dev = current_device();
+    TileWsParams wp = tile_ws_params(tp.f, c);
     wp.f.out = want_out ? out_scratch : nullptr;      // (the persistent kernel writes `out` on request only)
-    wp.perm = w.perm;
-    wp.tiles_per_pair = tp.tiles_per_pair;
-    wp.total_tiles = (int)total;
-    wp.rows_cap = tp.rows_cap;
-    wp.ovf_count = w.ovf_count;
-    wp.ovf_list = w.ovf_list;
-    wp.stats = w.stats;
-    wp.scales = w.scales;
-    wp.segs = w.segs;
-    wp.band = w.band;
-    wp.setprio = 0;
-    wp.prof = nullptr;
     wp.packed_w = reinterpret_cast<const unsigned *>(packed_w);
     wp.bias = bias;
     wp.x = x;
-    wp.err = w.err;
-    wp.tile_ctr = w.ovf_count + 2;
-    const int cus = device_cus(dev);
-    const unsigned grid = (unsigned)(total < cus ? total : cus);
-    if (tile_ws_band(desc)) {
-        if (wp.rows_cap > kTileRowsWsLarge) wp.rows_cap = kTileRowsWsLarge;
-        const size_t lds_ws = tile_ws_lds_bytes(kTileRowsWsLarge, desc->H, desc->W, true);
-        ET_GRANT_LDS((epipolar_fwd_tile_ws_kernel<kTileRowsWsLarge, 8, true, true>), lds_ws, dev);
-        hipLaunchKernelGGL((epipolar_fwd_tile_ws_kernel<kTileRowsWsLarge, 8, true, true>), dim3(grid),
-                           dim3((kWsMatrixWaves + 8) * kWave), lds_ws, st, wp);
-    } else {
-        const size_t lds_ws = tile_ws_lds_bytes(kTileRowsSmall, desc->H, desc->W);
-        ET_GRANT_LDS((epipolar_fwd_tile_ws_kernel<kTileRowsSmall, 8, true>), lds_ws, dev);
-        hipLaunchKernelGGL((epipolar_fwd_tile_ws_kernel<kTileRowsSmall, 8, true>), dim3(grid), dim3((kWsMatrixWaves + 8) * kWave),
-                           lds_ws, st, wp);
-    }
+    if (int e = launch_fwd_tile_ws<true>(desc, wp, dev, st)) return e;
     if (int e = check_launch("et_epipolar_forward_fused(ws)")) return e;
-    // the tiles it left over: `out` rows one block per tile, then their x rows
-    const int kpl = 1;
-    const int rows = tile_rows(desc);
-    const size_t lds = (size_t)(fwd_tile_array_floats(rows) + rows + kTilePix + 48 + kTilePix * 4) * 4 +
-                       (size_t)tp.hw_words * 8 + (kpl == 1 ? (size_t)kTilePix * kWave * 8 : 0);
-    const unsigned lgrid = (unsigned)(total < 2LL * cus ? total : 2LL * cus);
-    if (rows == kTileRowsLarge) {
-        ET_GRANT_LDS((epipolar_fwd_tile_list_kernel<1, kTileRowsLarge>), lds, dev);
-        hipLaunchKernelGGL((epipolar_fwd_tile_list_kernel<1, kTileRowsLarge>), dim3(lgrid), dim3(256), lds, st, tp);
-    } else {
-        ET_GRANT_LDS((epipolar_fwd_tile_list_kernel<1, kTileRowsSmall>), lds, dev);
-        hipLaunchKernelGGL((epipolar_fwd_tile_list_kernel<1, kTileRowsSmall>), dim3(lgrid), dim3(256), lds, st, tp);
-    }
+    // the tiles it left over: `out` rows one block per tile (K <= 64: one sample per lane), then their x rows
+    if (int e = launch_fwd_tile_list(tp, tile_rows(desc), 1, dev, st)) return e;
     if (int e = check_launch("et_epipolar_forward_fused(list)")) return e;
     // their x rows: the residual GEMM kernel over the list, two tiles per block and trip (round 6: the plain-fp32 kernel this replaces
     // took 76 us for the near-rectified rig's 640 left-over tiles -- 256 KB of weight fragments per eight pixel rows; now 24 us)
-    return et_internal_residual_rows_list(w.perm, w.ovf_list, w.ovf_count, tp.tiles_per_pair, HW, total, out_scratch, feat_ref,
+    return et_internal_residual_rows_list(c.w.perm, c.w.ovf_list, c.w.ovf_count, c.tiles_per_pair, c.HW, c.total, out_scratch, feat_ref,
                                           reinterpret_cast<const unsigned *>(packed_w), bias, x, st);
 }
 

@@ -1,12 +1,15 @@
-// Host-side helpers shared by the two tile translation units (et_forward_tile.hip, et_backward_tile.hip).
+// The host side of a tile call, shared by the two tile translation units (et_forward_tile.hip, et_backward_tile.hip):
+// eligibility, the workspace layout, begin_tile_call (checks, sizes, carved workspace), the ordering launches and the
+// launch helper of the tile kernels.  In the anonymous namespace: each unit instantiates its own copies.
 #pragma once
 #include <algorithm>
+#include "et_common.h"
 namespace {
+#include "kernels_tile_order.inc"   // kTilePix, kTileRows*, tile_keys_kernel, tile_order_kernel
+
 // The MFMA tile path applies to the 256-channel head when one reference pixel alone can never
 // overflow the tile's row array: a pixel's K samples touch at most 4K source pixels, and a line
 // through a W x H map at most 4 per column (or per row, whichever way it runs), i.e. 4 max(W, H).
-// one pixel's K samples touch at most 4K source pixels, and a line through a W x H map at most 4 per column (or per
-// row, whichever way it runs), i.e. 4 max(W, H)
 int tile_rows_per_pixel(const EtLayerDesc *d)
 {
     const int longest = d->W > d->H ? d->W : d->H;
@@ -115,8 +118,7 @@ int launch_tile_order(const EtLayerDesc *desc, const float *xs, const float *ys,
     const int perm_stride = tiles_per_pair * kTilePix;
     int n2 = 64;
     while (n2 < HW) n2 <<= 1;
-    const size_t lds_sort = order_uses_radix(n2) ? ((tile_order_lds_bytes(n2) + 15) & ~(size_t)15) + order_radix_extra_bytes(n2)
-                                                 : tile_order_lds_bytes(n2);
+    const size_t lds_sort = tile_order_lds_bytes(n2);
     const int dev = current_device();
     ET_GRANT_LDS(tile_order_kernel, lds_sort, dev);
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(w.segs);
@@ -128,5 +130,48 @@ int launch_tile_order(const EtLayerDesc *desc, const float *xs, const float *ys,
                        w.segs_pix, w.perm, feat_ref, feat_src, scales, ws_tables ? w.segs : (float4 *)nullptr,
                        ws_tables ? w.band : (float4 *)nullptr, clear, clear_vec4);
     return check_launch(who);
+}
+
+// What every tile call starts from: the sizes of the call and its carved workspace.
+struct TileCall {
+    int HW, tiles_per_pair, total, hw_words, rows_cap;
+    TileWorkspace w;
+};
+// The checks every tile export starts with, in this order -- the descriptor, `bad_args` (NULL, or what is wrong with the
+// export's own arguments), eligibility (`instead`: the export to use for other shapes), the workspace's size (the forward's
+// layout + `extra_bytes(pairs, pixels per map)` where given), the grid -- then the sizes and the carved workspace -> c.
+int begin_tile_call(const EtLayerDesc *desc, const char *who, const char *bad_args, const char *instead,
+                    size_t (*extra_bytes)(size_t, size_t), void *workspace, size_t workspace_bytes, TileCall *c)
+{
+    if (int e = validate(desc)) return e;
+    if (bad_args) return fail("%s: %s", who, bad_args);
+    if (!tile_eligible(desc))
+        return fail("%s: needs C == 256, H*W <= 16384 and 4 min(K, max(W,H)) <= %d (got C=%d H=%d W=%d K=%d); use %s", who,
+                    tile_rows_cap(desc), desc->C, desc->H, desc->W, desc->K, instead);
+    c->HW = desc->H * desc->W;
+    c->tiles_per_pair = (c->HW + kTilePix - 1) / kTilePix;
+    const long long total = (long long)c->tiles_per_pair * desc->N;
+    const size_t need = tile_workspace_words((size_t)total, (size_t)desc->N, (size_t)c->HW) * sizeof(int) + 256u +
+                        (extra_bytes ? extra_bytes((size_t)desc->N, (size_t)c->HW) : 0);
+    if (!workspace || workspace_bytes < need)
+        return fail("%s: workspace of %zu bytes is smaller than the %zu required", who, workspace ? workspace_bytes : (size_t)0, need);
+    // (one limit for both directions: kTilePix * total, the entries of perm, stays below 2^31 -- both index the same perm with
+    //  int tile numbers; the backward used to check `total` alone, a bound no workspace of the forward's layout reaches)
+    if (total > 0x7fffffffLL / kTilePix) return fail("grid too large");
+    c->total = (int)total;
+    c->hw_words = (c->HW + 31) / 32;
+    c->rows_cap = tile_rows_cap(desc);
+    c->w = carve_tile_workspace(workspace, (size_t)total, (size_t)desc->N, (size_t)c->HW);
+    return 0;
+}
+
+// Grants `lds` bytes of dynamic LDS to a kernel instance (once per instance, device and process) and launches it.
+template <auto Kernel, class Params>
+int launch_tile_kernel(const char *name, unsigned grid, unsigned block, size_t lds, int dev, hipStream_t st, const Params &params)
+{
+    static int granted[64];
+    if (int e = grant_lds(Kernel, lds, dev, granted, name)) return e;
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(block), lds, st, params);
+    return 0;
 }
 }  // namespace

@@ -1,5 +1,5 @@
 // Part of epipolar_kernels.hip (one translation unit, one anonymous namespace): the MFMA tile
-// formulation of the backward.  Not a stand-alone header; uses the helpers of kernels_forward_tile.inc.
+// formulation of the backward.  Not a stand-alone header.
 // ----------------------------------------------------------------------------
 // Same tiles, same row sets, same one 32 x (ROWS+1) LDS array as the forward (kernels_forward_tile.inc),
 // which is reused four times.  With g = d(out), f = feat_ref rows, F2_U the tile's source rows:
@@ -30,7 +30,8 @@
 // array holds their fp16 stage (SPLIT_D: merged kernels and 384 rows up), with the exact-fp32 forms as the fallback of a
 // tile whose source rows fail the fp16 guard.
 
-// (et_split_f16.h and the split D-type GEMM tile_gemm_rows_split come with kernels_forward_tile.inc)
+#pragma once
+#include "kernels_tile_common.inc"   // taps_of, row_runs / scatter_row, tile_gemm_* (and et_split_f16.h)
 
 // Row-array widths of the merged form (two arrays): 192 columns for maps up to 64 x 64 (three blocks per CU), 288 for
 // maps up to 96 x 96 (two, as the one-array kernel there); tiles with more rows are split into pixel groups.
@@ -45,6 +46,13 @@ constexpr int bwd_tile_array_floats(int rows)
     return bwd_rows_merged(rows)
                ? (2 * kTilePix * (rows + 1) > tile_array_floats(rows) ? 2 * kTilePix * (rows + 1) : tile_array_floats(rows))
                : tile_array_floats(rows);
+}
+// dynamic LDS of a block of ROWS = rows and KPL = kpl: what bwd_tile_body carves out of s_dyn -- the array(s), s_rows, s_pix,
+// s_misc[60], s_seg, bitmap + prefix of hw_words words each and, where the kernel keeps it (TAB), the table of sample locations
+constexpr size_t bwd_tile_lds_bytes(int rows, int hw_words, int kpl)
+{
+    return (size_t)(bwd_tile_array_floats(rows) + rows + kTilePix + 60 + kTilePix * 4) * 4 + (size_t)hw_words * 8 +
+           ((kpl == 1 && !bwd_rows_merged(rows)) ? (size_t)kTilePix * kWave * 8 : 0);
 }
 
 struct BwdTileParams {

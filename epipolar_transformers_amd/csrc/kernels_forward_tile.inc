@@ -1,5 +1,5 @@
-// Part of epipolar_kernels.hip (one translation unit, one anonymous namespace): the MFMA tile
-// formulation of the fused forward.  Not a stand-alone header.
+// Included inside the anonymous namespace of et_forward_tile.hip: the MFMA tile
+// formulation of the fused forward, one block per tile.
 // ----------------------------------------------------------------------------
 // Idea.  The per-pixel kernels are bound by VALU issue and by L1/TA bandwidth: every
 // reference pixel drags its ~220 source rows (1 KB each) through the vector pipeline on its
@@ -17,24 +17,13 @@
 // geometry / soft-max work.  D and B share one 32 x 257 LDS array.
 //
 //   tile_order_kernel        one block per pair: key = (line angle, line offset) of every
-//                            reference pixel's epipolar line, bitonic sort in LDS -> perm
+//                            reference pixel's epipolar line, bitonic sort in LDS -> perm   (kernels_tile_order.inc)
 //   epipolar_fwd_tile_kernel one block (4 waves) per tile
 //
 // Correctness never depends on the ordering: a tile whose row set exceeds the LDS array is
 // split into 2, 4, .. 32 pixel groups that are processed one after the other.
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kTilePix = 32;                    // reference pixels per tile (MFMA M)
-// Source rows a (sub)tile may touch = columns of the D/B array in LDS (template parameter ROWS of the kernel):
-// 256 for maps up to 64 x 64 (51.5 KB LDS, 3 blocks per CU), 384 for larger maps whose lines are longer
-// (68 KB, 2 blocks per CU; with 256 most tiles of a 96 x 96 map would overflow and split), 512 when one
-// pixel alone can touch more than 384 rows (K > 96 on maps above 96 x 96; 2 blocks per CU).  The array's
-// row stride is ROWS + 1: odd, so column reads are bank-conflict-free.
-constexpr int kTileRowsSmall = 256, kTileRowsLarge = 384, kTileRowsHuge = 512;
-// the warp-specialised persistent kernel above 64 x 64 (kernels_forward_tile_ws.inc, BT = true): 288-row arrays, maps up to
-// 96 x 96 (every tile of a 96 x 96 map has at most 280 rows; 384-row arrays do not fit its LDS)
-constexpr int kTileRowsWsLarge = 288, kWsMaxSideBand = 96, kWsMaxSideTwoPass = 128;
+#pragma once
+#include "kernels_tile_common.inc"   // taps_of, row_runs / scatter_row, tile_gemm_*
 
 struct TileParams {
     FwdParams f;
@@ -49,892 +38,15 @@ struct TileParams {
                             // tile then run as split-fp16 products (exact-fp32 redo of a tile whose rows overflow)
 };
 
-// ---- ordering ------------------------------------------------------------------------------
-// The sort's keys in LDS: one spare slot after every 16 (a thread's 8 keys of a small-stride round are then 17 slots from its
-// neighbour's, not 16: the 8-byte reads of a wave fall into different banks).
-__device__ __host__ constexpr int order_key_slot(int i) { return i + (i >> 4); }
-constexpr size_t tile_order_lds_bytes(int n2) { return (size_t)order_key_slot(n2) * sizeof(unsigned long long); }
-// S stages of the bitonic network (strides jj_top, jj_top / 2, ... jj_top >> (S - 1)) of the merge step k in one trip.
-// The keys are DOUBLES (an integer below 2^47 each: order_key below), kept as their bit patterns: a compare-exchange is then
-// v_min_f64 + v_max_f64 -- two instructions -- where 64-bit integer keys cost a compare and four selects; the kernel is bound by
-// exactly this arithmetic (one block per pair: 24 k compare-exchanges per stage on one compute unit).  A descending block sorts
-// the negated keys ascending (the sign bit flipped on the way in and out).
-__device__ __forceinline__ unsigned long long order_key(unsigned k32, int j)      // (line angle | line offset, pixel < 2^14)
-{
-    return (unsigned long long)__double_as_longlong((double)(((unsigned long long)k32 << 14) | (unsigned)j));
-}
-constexpr unsigned long long kOrderPadKey = 0x42E0000000000000ull;               // 2^47 as a double: behind every pixel
-__device__ __forceinline__ int order_key_pixel(unsigned long long bits)
-{
-    return (int)((unsigned long long)__longlong_as_double((long long)bits) & 0x3FFFull);
-}
-template <int S>
-__device__ __forceinline__ void order_sort_round(unsigned long long *s_key, int n2, int k, int jj_top)
-{
-    constexpr int R = 1 << S;
-    const int jlow = jj_top >> (S - 1);
-    for (int t = threadIdx.x; t < (n2 >> S); t += blockDim.x) {
-        const int base = ((t & ~(jlow - 1)) << S) | (t & (jlow - 1));    // S zero bits at the positions of the strides
-        const unsigned long long flip = (base & k) == 0 ? 0ull : 0x8000000000000000ull;   // (r * jlow < k: the same for all R keys)
-        double v[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) v[r] = __longlong_as_double((long long)(s_key[order_key_slot(base + r * jlow)] ^ flip));
-#pragma unroll
-        for (int st = S - 1; st >= 0; --st)
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-                if (!(r & (1 << st))) {
-                    const double a = v[r], b = v[r | (1 << st)];
-                    double lo, hi;
-                    asm("v_min_f64 %0, %1, %2" : "=v"(lo) : "v"(a), "v"(b));
-                    asm("v_max_f64 %0, %1, %2" : "=v"(hi) : "v"(a), "v"(b));
-                    v[r] = lo;
-                    v[r | (1 << st)] = hi;
-                }
-#pragma unroll
-        for (int r = 0; r < R; ++r) s_key[order_key_slot(base + r * jlow)] = (unsigned long long)__double_as_longlong(v[r]) ^ flip;
-    }
-    __syncthreads();
-}
-
-// ---- the same sort as a stable LSD radix sort (round 6; maps up to 64 x 64: n2 <= 4096) ----------------------------------
-// The bitonic network above costs 30 trips through LDS with a block barrier each, half the block's 1024 threads idle in every
-// trip: 37 us per call at 64 x 64 -- 3.4 % of the eval layer's step, on half the chip (one block per pair).  The keys are
-// (line angle 14 bits | line offset 16 bits | pixel 14 bits) with the pixels in ascending order to begin with, so a STABLE sort of
-// the upper 32 bits gives the same permutation (keys are unique: there is only one sorted order): four passes of 8 bits,
-//   1. every wave takes groups of 64 consecutive keys (group g = keys 64 g ..): the lanes with the same digit find each other with
-//      eight ballots -> rank inside the group, and the group's count of the digit goes to cnt[digit][g];
-//   2. an exclusive scan of cnt in (digit, group) order -- 16 counters per thread, a wave scan, 16 wave totals;
-//   3. key -> dst[cnt[digit][g] + rank].
-// Five barriers per pass, every thread busy in every phase.  Buffers: the bitonic sort's key array and a second one, ping-pong;
-// after the fourth pass the keys are back in the first, in the format the code below the sort expects.
-// MEASURED (profiles/r06_fwd_ab.txt, block 14): the same permutation bit for bit (scripts/dev/order_perm_dump.py), and SLOWER --
-// tile_order_kernel 37.1 -> 50.5 us at 64 x 64: the eight-ballot match is ~64 VALU instructions per key and pass (ballot, two
-// 64-bit selects, two ands per bit), ~500 per thread and pass with the scan, against ~60 per thread and trip of the network, whose
-// compare-exchange is two instructions.  Kept as an experiment, OFF.
-#ifndef ET_ORDER_RADIX
-#define ET_ORDER_RADIX 0            // (development: 1 = the radix sort for 256 .. 4096 keys)
-#endif
-constexpr int kOrderRadixMaxKeys = 4096, kOrderRadixMinKeys = 256;
-__host__ __device__ constexpr bool order_uses_radix(int n2) { return ET_ORDER_RADIX != 0 && n2 >= kOrderRadixMinKeys && n2 <= kOrderRadixMaxKeys; }
-// LDS beyond the bitonic key array: the second key buffer, cnt[256][n2 / 64] (16 bit) and 16 wave totals
-constexpr size_t order_radix_extra_bytes(int n2) { return (size_t)n2 * 8 + (size_t)256 * (n2 >> 6) * 2 + 64; }
-
-template <int PER>       // PER consecutive 16-bit counters per thread (PER = n2 / 256: 1, 2, 4, 8, 16)
-__device__ __forceinline__ void order_radix_scan(unsigned short *s_cnt, unsigned *s_wtot)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned v[PER];
-    if constexpr (PER == 1) {
-        v[0] = s_cnt[threadIdx.x];
-    } else {
-        const unsigned *src = reinterpret_cast<const unsigned *>(s_cnt) + threadIdx.x * (PER / 2);
-#pragma unroll
-        for (int i = 0; i < PER / 2; ++i) {
-            const unsigned w = src[i];
-            v[2 * i] = w & 0xFFFFu;
-            v[2 * i + 1] = w >> 16;
-        }
-    }
-    unsigned sum = 0;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-        const unsigned c = v[i];
-        v[i] = sum;                       // exclusive inside the thread
-        sum += c;
-    }
-    unsigned incl = sum;
-#pragma unroll
-    for (int m = 1; m < kWave; m <<= 1) {
-        const unsigned o = __shfl_up(incl, m);
-        if (lane >= m) incl += o;
-    }
-    if (lane == kWave - 1) s_wtot[wave] = incl;
-    __syncthreads();
-    unsigned base = incl - sum;
-    for (int w = 0; w < wave; ++w) base += s_wtot[w];
-    if constexpr (PER == 1) {
-        s_cnt[threadIdx.x] = (unsigned short)(base + v[0]);
-    } else {
-        unsigned *dst = reinterpret_cast<unsigned *>(s_cnt) + threadIdx.x * (PER / 2);
-#pragma unroll
-        for (int i = 0; i < PER / 2; ++i) dst[i] = ((base + v[2 * i]) & 0xFFFFu) | ((base + v[2 * i + 1]) << 16);
-    }
-}
-
-// s_key: the bitonic sort's array (order_key_slot indexing), loaded with the keys of tile_keys_kernel (pads behind HW); 1024 threads
-__device__ __forceinline__ void order_radix_sort(unsigned long long *s_key, int n2, int HW)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int G = n2 >> 6;                                                  // groups of 64 keys
-    unsigned long long *s_b = s_key + ((order_key_slot(n2) + 1) & ~1);      // second buffer, plain indexing
-    unsigned short *s_cnt = reinterpret_cast<unsigned short *>(s_b + n2);   // [256][G]
-    unsigned *s_wtot = reinterpret_cast<unsigned *>(s_cnt + 256 * G);       // [16]
-    constexpr int kRounds = kOrderRadixMaxKeys / 64 / 16;                   // groups per wave: 4
-    const unsigned long long lt = (1ull << lane) - 1ull;
-#pragma unroll 1
-    for (int pass = 0; pass < 4; ++pass) {
-        const bool fwd = (pass & 1) == 0;                                   // s_key -> s_b, then back
-        for (int i = threadIdx.x; i < 128 * G; i += blockDim.x) reinterpret_cast<unsigned *>(s_cnt)[i] = 0u;
-        unsigned long long key[kRounds];
-        int dgt[kRounds], rank[kRounds], cnt[kRounds];
-#pragma unroll
-        for (int r = 0; r < kRounds; ++r) {
-            const int g = wave + 16 * r;
-            dgt[r] = rank[r] = cnt[r] = 0;
-            key[r] = 0ull;
-            if (g < G) {                                                    // wave-uniform
-                const int i = g * kWave + lane;
-                unsigned long long k = fwd ? s_key[order_key_slot(i)] : s_b[i];
-                if (pass == 0) {
-                    // the double's integer value (k32 << 14 | pixel); a pad gets the key of a pixel without a segment -- it
-                    // starts behind every pixel and the sort is stable, so it stays behind them
-                    k = (i < HW) ? (unsigned long long)__longlong_as_double((long long)k) : ((0xFFFFFFFFull << 14) | (unsigned)i);
-                }
-                key[r] = k;
-                const int d8 = (int)(k >> (14 + 8 * pass)) & 255;
-                unsigned long long peers = ~0ull;
-#pragma unroll
-                for (int b = 0; b < 8; ++b) {
-                    const bool bit = (d8 >> b) & 1;
-                    const unsigned long long bal = __builtin_amdgcn_ballot_w64(bit);
-                    peers &= bit ? bal : ~bal;
-                }
-                dgt[r] = d8;
-                rank[r] = __popcll(peers & lt);
-                cnt[r] = __popcll(peers);
-            }
-        }
-        __syncthreads();                                                    // (the counters are clear)
-#pragma unroll
-        for (int r = 0; r < kRounds; ++r) {
-            const int g = wave + 16 * r;
-            if (g < G && rank[r] == 0) s_cnt[dgt[r] * G + g] = (unsigned short)cnt[r];
-        }
-        __syncthreads();
-        switch (G) {                                                        // 256 G counters over 1024 threads
-        case 64: order_radix_scan<16>(s_cnt, s_wtot); break;
-        case 32: order_radix_scan<8>(s_cnt, s_wtot); break;
-        case 16: order_radix_scan<4>(s_cnt, s_wtot); break;
-        case 8: order_radix_scan<2>(s_cnt, s_wtot); break;
-        default: order_radix_scan<1>(s_cnt, s_wtot); break;                 // G == 4
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < kRounds; ++r) {
-            const int g = wave + 16 * r;
-            if (g < G) {
-                const int pos = (int)s_cnt[dgt[r] * G + g] + rank[r];
-                if (pass == 3) {                                            // back to the format of the bitonic sort's result
-                    const int pix = (int)(key[r] & 0x3FFFull);
-                    s_key[order_key_slot(pos)] = (pix < HW) ? order_key((unsigned)(key[r] >> 14), pix) : kOrderPadKey;
-                } else if (fwd) {
-                    s_b[pos] = key[r];
-                } else {
-                    s_key[order_key_slot(pos)] = key[r];
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// The ordering runs as TWO kernels: the per-pixel part (segment, sort key) over the whole device, then one block per pair
-// for the part that needs a pair's keys together.  As one kernel (rounds 1-4) a pair's 4096 segments, atan2f / sincosf keys
-// and, after the sort, the segments again were all computed by ONE compute unit: ~6000 VALU instructions per wave x 16 waves,
-// 50 us of a 0.93 ms forward (profiles/r04_*kernel_stats.csv), 180-210 us at 96 x 96 / 128 x 128.
-//   keys[n * 2 * perm_stride + j], j < HW : the sort key of pixel j (the region of pair n's ordered segments: consumed by
-//                                           block n of tile_order_kernel before it writes them)
-//   segs_pix[n * HW + j]                  : its epipolar segment
-__global__ __launch_bounds__(256) void tile_keys_kernel(const EtLayerDesc d, const float *__restrict__ xs,
-                                                        const float *__restrict__ ys, const float *__restrict__ cam_all,
-                                                        int perm_stride, unsigned long long *__restrict__ keys,
-                                                        float4 *__restrict__ segs_pix, int *__restrict__ zero_word)
-{
-    const int HW = d.H * d.W;
-    const int blocks_per_pair = (HW + (int)blockDim.x - 1) / (int)blockDim.x;
-    const int n = blockIdx.x / blocks_per_pair, j = (blockIdx.x - n * blocks_per_pair) * blockDim.x + threadIdx.x;
-    // the forward's workspace header: [0] overflow-tile counter, [2..9] the per-XCD tile counters of the persistent kernel
-    // ([1] is the STICKY error word: never cleared here)
-    if (zero_word && blockIdx.x == 0 && threadIdx.x < 10 && threadIdx.x != 1) zero_word[threadIdx.x] = 0;
-    if (j >= HW) return;
-    const float *cam = cam_all + (size_t)n * ET_CAM_STRIDE;
-    const float cx = 0.5f * (d.xmin + d.xmax), cy = 0.5f * (d.ymin + d.ymax);
-    const float rmax = 0.5f * sqrtf((d.xmax - d.xmin) * (d.xmax - d.xmin) + (d.ymax - d.ymin) * (d.ymax - d.ymin)) + 1.f;
-    const float kPi = 3.14159265358979f;
-    // Every epipolar line of the pair passes through the epipole e2, so a line is determined by its direction, and the
-    // directions towards the image form a fan around the direction from e2 to the image centre.  Angles are compared
-    // modulo pi: measured from a fixed axis the fan can straddle 0 = pi, and the sorted sequence then jumps from one
-    // end of the fan to the other in the MIDDLE of the list -- one tile per pair got lines from both ends (twice the rows;
-    // its taps fit no common band: round 4's column masks sent it to the overflow list).  Measured from the fan's own
-    // axis the jump sits at the ends of the list, where it belongs.
-    float th0 = atan2f(cy - cam[25], cx - cam[24]);
-    if (!(fabsf(th0) <= 4.f)) th0 = 0.f;                 // (epipole at infinity / not finite: any origin will do)
-    const int h = j / d.W, w = j - h * d.W;
-    const et::Segment seg = et::epipolar_segment(d, cam, xs[w], ys[h]);
-    unsigned k32 = 0xFFFFFFFFu;  // pixels without a segment go last
-    if (seg.vx != 0.f || seg.vy != 0.f) {
-        float th = atan2f(seg.vy, seg.vx);
-        if (th < 0.f) th += kPi;
-        if (th >= kPi) th -= kPi;
-        float sn, cs;
-        sincosf(th, &sn, &cs);
-        const float rho = (seg.sy - cy) * cs - (seg.sx - cx) * sn;  // signed offset from the image centre
-        float tk = th - th0 + 0.5f * kPi;                       // the fan's axis at pi / 2
-        tk -= kPi * floorf(tk * (1.f / kPi));
-        const int tb = min(16383, max(0, (int)(tk * (16384.f / kPi))));
-        const int rq = min(65535, max(0, (int)((rho / rmax * 0.5f + 0.5f) * 65535.f)));
-        k32 = ((unsigned)tb << 16) | (unsigned)rq;
-    }
-    keys[(size_t)n * 2 * perm_stride + j] = order_key(k32, j);
-    segs_pix[(size_t)n * HW + j] = make_float4(seg.sx, seg.sy, seg.vx, seg.vy);
-}
-
-__global__ __launch_bounds__(1024) void tile_order_kernel(const EtLayerDesc d, int n2, int perm_stride,
-                                                          const unsigned long long *__restrict__ keys,
-                                                          const float4 *__restrict__ segs_pix, int *__restrict__ perm,
-                                                          const float *__restrict__ fref = nullptr,
-                                                          const float *__restrict__ fsrc = nullptr,
-                                                          float *__restrict__ scales = nullptr,
-                                                          float4 *__restrict__ segs = nullptr,
-                                                          float4 *__restrict__ band = nullptr,
-                                                          float4 *__restrict__ clear = nullptr, size_t clear_vec4 = 0)
-{
-    extern __shared__ unsigned long long s_key[];
-    // Blocks beyond the pairs (the backward's launch): clear `clear` (grad_src, which the tile kernel adds into) BESIDE the
-    // sort -- the sort keeps N compute units busy with LDS latency, the clearing is HBM stores: one after the other they
-    // cost their sum (hipMemsetAsync + this kernel), together the longer of the two.
-    if (blockIdx.x >= (unsigned)d.N) {
-        const size_t nblk = gridDim.x - d.N, first = (size_t)(blockIdx.x - d.N) * blockDim.x + threadIdx.x;
-        for (size_t i = first; i < clear_vec4; i += nblk * blockDim.x) clear[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        return;
-    }
-    const int n = blockIdx.x;
-    const int HW = d.H * d.W;
-    // Power-of-two scales for the split-fp16 GEMMs of the warp-specialised forward (C == 256): an ESTIMATE of each
-    // map's largest magnitude from 64 whole pixel rows spread over the map, placed at 2^10 -- fp16 then has a factor
-    // 32 to 64 of headroom above it, and the kernel checks every value it converts (a tile that would overflow is
-    // redone in exact fp32).  scales[n] = { s_ref, 1 / s_ref, s_src, 1 / s_src }.  (The loads go out first: their
-    // latency passes behind the sort.)
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float m[2] = {0.f, 0.f};
-    if (scales) {
-        const int pstep = max(1, HW / 64);
-        for (int which = 0; which < 2; ++which) {
-            const float4 *map = reinterpret_cast<const float4 *>((which ? fsrc : fref) + (size_t)n * HW * d.C);
-            for (int k = wave; k < 64; k += 16) {
-                const int pix = min(k * pstep, HW - 1);
-                const float4 v = map[(size_t)pix * (d.C >> 2) + (lane % (d.C >> 2))];
-                m[which] = fmaxf(m[which], fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-            }
-        }
-    }
-    for (int j = threadIdx.x; j < n2; j += blockDim.x)
-        s_key[order_key_slot(j)] = (j < HW) ? keys[(size_t)n * 2 * perm_stride + j] : kOrderPadKey;
-    __syncthreads();
-    // Bitonic sort, up to three stages (strides jj, jj / 2, jj / 4) per trip through LDS: a thread takes the 8 keys that
-    // differ in those three index bits, runs the stages in registers and puts them back -- 30 trips (and block barriers)
-    // instead of 78 for a 64 x 64 map, a third of the LDS traffic (one block per pair: the kernel is bound by the LDS
-    // pipe and the barrier latency of a single CU).  Same comparisons, same result as one stage per pass.
-    if (order_uses_radix(n2)) {
-        order_radix_sort(s_key, n2, HW);                 // (the same permutation: keys are unique)
-    } else {
-    for (int k = 2; k <= n2; k <<= 1) {
-        int jj = k >> 1;
-        while (jj > 0) {
-            if (jj >= 4) {
-                order_sort_round<3>(s_key, n2, k, jj);
-                jj >>= 3;
-            } else if (jj == 2) {
-                order_sort_round<2>(s_key, n2, k, jj);
-                jj = 0;
-            } else {
-                order_sort_round<1>(s_key, n2, k, jj);
-                jj = 0;
-            }
-        }
-    }
-    }
-    const float4 *pair_segs = segs_pix + (size_t)n * HW;
-    for (int j = threadIdx.x; j < perm_stride; j += blockDim.x) {
-        const int pix = (j < HW) ? order_key_pixel(s_key[order_key_slot(j)]) : -1;
-        perm[(size_t)n * perm_stride + j] = pix;
-        // the segments again, in tile order: the warp-specialised forward reads them instead of recomputing
-        if (segs) segs[(size_t)n * perm_stride + j] = pix >= 0 ? pair_segs[pix] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    // The tile's base line (warp-specialised forward), in tap space, as minor = a + b * major along the axis the tile's
-    // lines mostly run: the kernel keeps the tile's row set as one 16-bit mask per column u of the major axis, bit i <->
-    // minor coordinate floor(a + b u) - 1 + i, so the base line has to lie BELOW every line of the tile in every column.
-    // The lines of a pair form a pencil through the epipole and the tile's pixels are sorted by angle, so at any column the
-    // tile's lines lie between its first and its last (valid) pixel's; the base line is the chord of the lower envelope
-    // min(first, last) between the two ends of the map -- the envelope is concave, the chord never above it.  (Rounds 2-4 took
-    // the first pixel's line itself: right for an epipole far outside the map -- the ring rig: the lines of a tile do not
-    // cross inside the map and the first is the lowest everywhere -- but with the epipole INSIDE or at the edge of the map the
-    // lines cross there, the later ones lie below the first on one side, and three tiles in four went to the overflow list;
-    // tests/test_gpu_rigs.py.)  Pixels without a segment sort last: a tile whose first pixel has none touches nothing.
-    if (band) {
-        auto line_of = [&](const float4 &v, bool force, bool xm_in, float &a, float &b, bool &xm) -> bool {
-            et::Segment sg;
-            sg.sx = v.x; sg.sy = v.y; sg.vx = v.z; sg.vy = v.w;
-            float nx0, ny0, nx1, ny1;
-            et::sample_location<false>(d, sg, 0.f, et::Pow2Recips(), nx0, ny0);
-            et::sample_location<false>(d, sg, 1.f, et::Pow2Recips(), nx1, ny1);
-            const float x0 = et::unnormalize(nx0, d.W, d.align_corners), y0 = et::unnormalize(ny0, d.H, d.align_corners);
-            const float dx = et::unnormalize(nx1, d.W, d.align_corners) - x0;
-            const float dy = et::unnormalize(ny1, d.H, d.align_corners) - y0;
-            xm = force ? xm_in : fabsf(dx) >= fabsf(dy);
-            a = b = 0.f;
-            if (xm) {
-                if (dx != 0.f) b = dy / dx;
-                else if (force) return false;
-                a = y0 - b * x0;
-            } else {
-                if (dy == 0.f) return false;
-                b = dx / dy;
-                a = x0 - b * y0;
-            }
-            return fabsf(a) < 1e6f && fabsf(b) <= 4.f;
-        };
-        for (int t = threadIdx.x; t < perm_stride / kTilePix; t += blockDim.x) {
-            const int j = t * kTilePix;
-            const int pix = (j < HW) ? order_key_pixel(s_key[order_key_slot(j)]) : -1;
-            float a = 0.f, b = 0.f, xmaj = 1.f;
-            if (pix >= 0) {
-                const float4 v = pair_segs[pix];
-                bool xm = true;
-                if ((v.z != 0.f || v.w != 0.f) && line_of(v, false, true, a, b, xm)) {
-                    xmaj = xm ? 1.f : 0.f;
-                    // the tile's last pixel with a segment
-                    float4 vl = v;
-                    for (int jj = min(j + kTilePix, HW) - 1; jj > j; --jj) {
-                        const float4 c = pair_segs[order_key_pixel(s_key[order_key_slot(jj)])];
-                        if (c.z != 0.f || c.w != 0.f) {
-                            vl = c;
-                            break;
-                        }
-                    }
-                    float a2, b2;
-                    bool xm2;
-                    if (line_of(vl, true, xm, a2, b2, xm2)) {
-                        // columns -1 .. umax (the taps of a sample reach one column beyond the map on either side)
-                        const float ulo = -1.f, uhi = (float)(xm ? d.W : d.H);
-                        const float m0 = fminf(a + b * ulo, a2 + b2 * ulo), m1 = fminf(a + b * uhi, a2 + b2 * uhi);
-                        b = (m1 - m0) / (uhi - ulo);
-                        a = m0 - b * ulo;
-                    }
-                    if (!(fabsf(a) < 1e6f)) a = 0.f, b = 0.f;   // (never with a finite segment; keeps the int conversions defined)
-                } else {
-                    a = 0.f, b = 0.f;
-                }
-            }
-            band[(size_t)n * (perm_stride / kTilePix) + t] = make_float4(a, b, xmaj, 0.f);
-        }
-    }
-    if (scales) {
-        __syncthreads();
-        float *s_red = reinterpret_cast<float *>(s_key);
-        for (int which = 0; which < 2; ++which) {
-            for (int o = 32; o >= 1; o >>= 1) m[which] = fmaxf(m[which], __shfl_xor(m[which], o));
-            if (lane == 0) s_red[which * 16 + wave] = m[which];
-        }
-        __syncthreads();
-        if (threadIdx.x < 2) {
-            float mx = 0.f;
-            for (int w = 0; w < 16; ++w) mx = fmaxf(mx, s_red[threadIdx.x * 16 + w]);
-            int e = 0;
-            float sc = 1.f;
-            if (mx > 0.f && mx < 3e38f) {
-                frexpf(mx, &e);                               // mx = f * 2^e, f in [0.5, 1)
-                e = min(60, max(-60, 11 - e));                // mx * 2^(11 - e) in [2^10, 2^11)
-                sc = ldexpf(1.f, e);
-            }
-            scales[n * 4 + threadIdx.x * 2] = sc;
-            scales[n * 4 + threadIdx.x * 2 + 1] = 1.f / sc;
-        }
-    }
-}
-
-#include "et_wave_reduce.h"
-
-// The four bilinear taps of a sample from its normalised location: the same arithmetic (and
-// rounding) as the tail of et::sample_setup, in plain nw / ne / sw / se order.
-struct TapSet {
-    int tap[4];     // linear source pixel index, -1 outside the image
-    float w[4];     // bilinear weight, 0 outside the image
-    int cell;       // id of the sample's 2x2 cell (same id <=> same four taps); unique per lane when !in
-};
-__device__ __forceinline__ TapSet taps_of(const EtLayerDesc &d, float nx, float ny, bool in)
-{
-    const float x = et::unnormalize(nx, d.W, d.align_corners);
-    const float y = et::unnormalize(ny, d.H, d.align_corners);
-    const float xw = floorf(x), yn = floorf(y);
-    const float w = x - xw, e = 1.f - w, n = y - yn, so = 1.f - n;
-    const int x0 = (int)fminf(fmaxf(xw, -2.f), (float)d.W);
-    const int y0 = (int)fminf(fmaxf(yn, -2.f), (float)d.H);
-    TapSet o;
-    o.cell = in ? y0 * 32768 + x0 : -(1 << 30) - (int)(threadIdx.x & 63);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int tx = t & 1, ty = t >> 1;
-        const int xx = x0 + tx, yy = y0 + ty;
-        const bool ok = in && ((unsigned)xx < (unsigned)d.W) && ((unsigned)yy < (unsigned)d.H);
-        o.w[t] = ok ? (ty ? n : so) * (tx ? w : e) : 0.f;
-        o.tap[t] = ok ? yy * d.W + xx : -1;
-    }
-    return o;
-}
-
-// Building a B row (array row of one pixel := sum over its samples of coef_k * w_kt on the row slots) without
-// LDS atomics.  Consecutive samples that fall into the same 2x2 cell share all four taps, and a cell is never
-// revisited along the line, so within one tap stream equal slots only occur in runs of neighbouring lanes.
-// RowRuns holds the run structure (shared by the four streams); for runs of at most two samples each stream
-// is one DPP add + a plain read-modify-write by the last lane of every run (distinct slots, no conflicts).
-// ds_add_f32 costs ~70 clocks of the CU-wide LDS pipe per wave instruction; pixels with longer runs (short
-// epipolar segments) keep the atomic form.
-struct RowRuns {
-    bool same;   // this lane's cell == the previous lane's
-    bool end;    // last lane of its run
-    bool longer; // wave-uniform: some run has three or more samples
-};
-__device__ __forceinline__ RowRuns row_runs(int cell)
-{
-    const int p1 = __builtin_amdgcn_update_dpp(-1, cell, 0x138, 0xf, 0xf, false);  // wave_shr:1
-    const int p2 = __builtin_amdgcn_update_dpp(-1, p1, 0x138, 0xf, 0xf, false);
-    const int n1 = __builtin_amdgcn_update_dpp(-1, cell, 0x130, 0xf, 0xf, false);  // wave_shl:1
-    RowRuns r;
-    r.same = p1 == cell;
-    r.end = n1 != cell;
-    r.longer = __builtin_amdgcn_ballot_w64(r.same && p2 == cell) != 0;
-    return r;
-}
-__device__ __forceinline__ void scatter_row(float *drow, const int (&sl)[4], const float (&val)[4], const RowRuns &rr, int pad)
-{
-    if (rr.longer) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) atomicAdd(&drow[sl[r]], val[r]);
-        return;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float pv = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(val[r]), 0x138, 0xf, 0xf, false));
-        const float sum = rr.same ? val[r] + pv : val[r];
-        if (rr.end && sl[r] != pad) drow[sl[r]] += sum;
-    }
-}
-
-// ---- the D-type GEMM of a tile: array = A_t . F2_U^T --------------------------------------------------------
-// A_t = the tile's 32 rows of `abuf` (feat_ref for the similarity, grad_out for the backward's g . S_k), F2_U the
-// tile's U source rows.  Fragment layout of v_mfma_f32_32x32x2_f32: lane l supplies A[m = l & 31][k = l >> 5] and
-// B[k = l >> 5][n = l & 31].  The k order is ours to choose as long as A and B agree: MFMA number 4q + t contracts
-// channels 8q + t (lanes 0-31) and 8q + 4 + t (lanes 32-63), so each lane feeds four MFMAs from ONE 16-byte load,
-// straight from global memory (no LDS staging).  Loads run kStages ahead of the MFMAs; sched_barriers pin the
-// order (left alone, the scheduler sinks every load next to its use and the matrix pipe waits a full memory
-// latency per 8 MFMAs).
-//
-// Work split over the block's four waves (one per SIMD): whole 32-row blocks, two at a time per wave (shared A
-// fragment, two independent accumulators).  With U ~ 155 that is five blocks for four waves -- one SIMD idle, one
-// padded block -- but the phase is bound by operand traffic from L2 (every wave re-reads the 32 KB A tile), not by
-// the MFMA makespan: dealing the blocks out evenly (whole block + a channel half of a fifth/sixth block per wave,
-// the halves meeting in spare array columns) was measured and changed nothing; (row block, channel half) units
-// meeting through ds_add_f32 cost +0.7 ms; 16 x 16 x 4 MFMA blocks +0.16 ms (1.7x the operand traffic).
-// When every wave has at most one pair of row blocks (nb <= 8) the A tile is first staged ONCE in LDS -- in the
-// D/B array itself, which is idle until the results are written -- and the waves read their A fragments from
-// there: the tile then pulls ~190 KB instead of ~290 KB from L2 in this phase.
-constexpr int kAStride = 260;  // floats per staged A row: 16-byte aligned rows, b128 fragment reads conflict-free
-constexpr int tile_array_floats(int rows) { return kTilePix * (rows + 1 > kAStride ? rows + 1 : kAStride); }
 // the forward's array: rows of ROWS + 4 floats (16-byte aligned: the split second GEMM reads 16-byte fragments), and at
 // least the 2 x 32 x 528 bytes of fp16 stage of the split first GEMM
 constexpr int fwd_tile_array_floats(int rows) { return kTilePix * (rows + 4) > 8448 ? kTilePix * (rows + 4) : 8448; }
-
-// on_a_ready(staged): called once by every thread when the A tile can be read (staged = true: from LDS, row i at
-// s_D + i * kAStride), before any MFMA -- the forward copies its res_base rows there.
-template <int STRIDE, class OnAReady>
-__device__ __forceinline__ void tile_gemm_rows(const __amdgpu_buffer_rsrc_t abuf, const __amdgpu_buffer_rsrc_t src,
-                                               int abase, int stage_off, const int *s_rows, float *s_D, int U, int nb,
-                                               int tid, int wave, int li, int lh, OnAReady &&on_a_ready)
+// dynamic LDS of a block of ROWS = rows and KPL = kpl: what fwd_tile_body carves out of s_dyn -- the array, s_rows, s_pix,
+// s_misc[48], s_seg, bitmap + prefix of hw_words words each and, KPL == 1, the table of sample locations
+constexpr size_t fwd_tile_lds_bytes(int rows, int hw_words, int kpl)
 {
-    constexpr int kRowBytes = 1024, kStages = 4;
-    if (nb <= 2 * kWavesPerBlock) {
-        // thread t stages 128 bytes of A row t >> 3 (stage_off: its byte offset in `abuf`, past the end for a pixel
-        // outside the group: zeros)
-        {
-            float4 st[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) st[k] = buf_load_f4(abuf, stage_off + k * 16, 0);
-            float *arow = s_D + (tid >> 3) * kAStride + (tid & 7) * 32;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) *reinterpret_cast<float4 *>(arow + k * 4) = st[k];
-        }
-        __syncthreads();
-        on_a_ready(true);
-        // Wave w: the 32-row blocks 2 w, 2 w + 1 = four 16-row quarters, each against the two 16-pixel halves of the
-        // tile (v_mfma_f32_16x16x4_f32).  The load path merges the addresses of a lane QUAD only
-        // (scripts/micro/load_patterns.hip: an instruction whose quads read 64 contiguous bytes runs at 32-40 B/clk per
-        // CU; in operand order -- lane n = row n, neighbouring lanes 1 KB apart -- at 15 B/clk, which is what bounded
-        // this phase): a lane LOADS 16 bytes of row (lane >> 2), chunk (lane & 3) of a 64-byte segment, and
-        // ds_bpermute (the LDS crossbar, no LDS memory) hands lane (n, kg) = (lane & 15, lane >> 4) the registers of
-        // lane 4 n + kg: chunk kg of row n = the operand of the four MFMAs of the segment (k = kg <-> channel
-        // 16 seg + 4 kg + w in MFMA w; the A fragment is the matching 16 bytes of the staged tile).
-        typedef float f32x4_t __attribute__((ext_vector_type(4)));
-        const int jb = 2 * wave;
-        const bool work = jb < nb;
-        f32x4_t acc[2][4];     // [pixel half][row quarter]
-#pragma unroll
-        for (int t = 0; t < 8; ++t) acc[t >> 2][t & 3] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-        const int ln = (li & 15), lk = (lh << 1) | (li >> 4);      // lane & 15, lane >> 4
-        if (work) {
-            const int lane_ = li + 32 * lh;
-            const int paddr = (4 * ln + lk) * 4;
-            int offh[4];
-#pragma unroll
-            for (int hh = 0; hh < 4; ++hh)
-                offh[hh] = s_rows[min(jb * 32 + hh * 16 + (lane_ >> 2), U - 1)] * kRowBytes + (lane_ & 3) * 16;
-            const float *afrag = s_D + ln * kAStride + lk * 4;
-            constexpr int kSegStages = 2;
-            float4 b[kSegStages][4];
-#pragma unroll
-            for (int q = 0; q < kSegStages; ++q)
-#pragma unroll
-                for (int hh = 0; hh < 4; ++hh) b[q][hh] = buf_load_f4(src, offh[hh] + q * 64, 0);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const float4 xa0 = *reinterpret_cast<const float4 *>(afrag + q * 16);
-                const float4 xa1 = *reinterpret_cast<const float4 *>(afrag + 16 * kAStride + q * 16);
-#pragma unroll
-                for (int hh = 0; hh < 4; ++hh) {
-                    const float4 x = b[q % kSegStages][hh];
-                    const float px = __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(x.x)));
-                    const float py = __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(x.y)));
-                    const float pz = __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(x.z)));
-                    const float pw = __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(x.w)));
-                    acc[0][hh] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa0.x, px, acc[0][hh], 0, 0, 0);
-                    acc[1][hh] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa1.x, px, acc[1][hh], 0, 0, 0);
-                    acc[0][hh] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa0.y, py, acc[0][hh], 0, 0, 0);
-                    acc[1][hh] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa1.y, py, acc[1][hh], 0, 0, 0);
-                    acc[0][hh] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa0.z, pz, acc[0][hh], 0, 0, 0);
-                    acc[1][hh] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa1.z, pz, acc[1][hh], 0, 0, 0);
-                    acc[0][hh] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa0.w, pw, acc[0][hh], 0, 0, 0);
-                    acc[1][hh] = __builtin_amdgcn_mfma_f32_16x16x4f32(xa1.w, pw, acc[1][hh], 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (q + kSegStages < 16) {
-#pragma unroll
-                    for (int hh = 0; hh < 4; ++hh) b[q % kSegStages][hh] = buf_load_f4(src, offh[hh] + (q + kSegStages) * 64, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        __syncthreads();  // every wave is done with the staged A tile: the array may take the results
-        if (work) {
-            const bool has1 = jb + 1 < nb;
-            float *drow = s_D + (4 * lk) * STRIDE + jb * 32 + ln;
-#pragma unroll
-            for (int g = 0; g < 2; ++g)
-#pragma unroll
-                for (int hh = 0; hh < 4; ++hh) {
-                    if (hh >= 2 && !has1) continue;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) drow[(16 * g + r) * STRIDE + 16 * hh] = acc[g][hh][r];
-                }
-        }
-        return;
-    }
-    on_a_ready(false);
-    for (int jb = 2 * wave; jb < nb; jb += 2 * kWavesPerBlock) {
-        const int off0 = s_rows[min(jb * 32 + li, U - 1)] * kRowBytes + lh * 16;
-        const int off1 = s_rows[min(jb * 32 + 32 + li, U - 1)] * kRowBytes + lh * 16;
-        f32x16 acc0, acc1;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            acc0[r] = 0.f;
-            acc1[r] = 0.f;
-        }
-        float4 av[kStages], b0[kStages], b1[kStages];
-#pragma unroll
-        for (int q = 0; q < kStages; ++q) {
-            av[q] = buf_load_f4(abuf, abase + q * 32, 0);
-            b0[q] = buf_load_f4(src, off0 + q * 32, 0);
-            b1[q] = buf_load_f4(src, off1 + q * 32, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < 32; ++q) {
-            const float4 x0 = b0[q % kStages], x1 = b1[q % kStages];
-            const float4 xa = av[q % kStages];
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(xa.x, x0.x, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(xa.x, x1.x, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(xa.y, x0.y, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(xa.y, x1.y, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(xa.z, x0.z, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(xa.z, x1.z, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(xa.w, x0.w, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(xa.w, x1.w, acc1, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (q + kStages < 32) {
-                av[q % kStages] = buf_load_f4(abuf, abase + (q + kStages) * 32, 0);
-                b0[q % kStages] = buf_load_f4(src, off0 + (q + kStages) * 32, 0);
-                b1[q % kStages] = buf_load_f4(src, off1 + (q + kStages) * 32, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        const bool has1 = jb + 1 < nb;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = (r & 3) + 8 * (r >> 2) + 4 * lh;
-            s_D[m * STRIDE + jb * 32 + li] = acc0[r];
-            if (has1) s_D[m * STRIDE + jb * 32 + 32 + li] = acc1[r];
-        }
-    }
-}
-
-// ---- the D-type GEMM (array = A_t . F2_U^T) as split-fp16 products ------------------------------------------------
-// Same work split and load scheme as tile_gemm_rows (wave w: the 32-row blocks 2 w, 2 w + 1 of every pass of eight blocks,
-// as four 16-row quarters; quad-contiguous loads rearranged by ds_bpermute) on v_mfma_f32_16x16x32_f16: 24 MFMAs of 16
-// cycles per 32 channels instead of 64 fp32 MFMAs of 32.  The A tile is staged ONCE as fp16 hi | lo (in the k order of the
-// B operand), every row under the power of two of its own exact maximum (1 / scale -> s_red[32]); the source rows are scaled by the
-// per-pair ESTIMATE `s_src` (tile_order_kernel) and every converted value is checked: the function returns true (for this
-// wave) if one is beyond fp16's range -- the caller then redoes the tile with the exact fp32 tile_gemm_rows.  Needs
-// 2 x 32 x 528 bytes of stage at the start of the array (the results replace it at the end: no trailing barrier, like
-// tile_gemm_rows).  PASSES = passes of eight 32-row blocks (1: U <= 256; 2: U <= 512); the accumulators of all passes
-// stay in registers until every wave is done with the stage.
-#include "et_split_f16.h"
-template <int STRIDE, int PASSES>
-__device__ __forceinline__ bool tile_gemm_rows_split(const __amdgpu_buffer_rsrc_t abuf, const __amdgpu_buffer_rsrc_t src,
-                                                     int stage_off, const int *s_rows, float *s_D, float *s_red, int U, int nb,
-                                                     int tid, int wave, int lane, float s_src, float inv_src)
-{
-    constexpr int kRowBytes = 1024, kStageRow = 528;
-    char *s_hi = reinterpret_cast<char *>(s_D), *s_lo = s_hi + kTilePix * kStageRow;
-    {
-        float4 st[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) st[k] = buf_load_f4(abuf, stage_off + k * 16, 0);
-        float m = 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) m = fmaxf(m, fmaxf(fmaxf(fabsf(st[k].x), fabsf(st[k].y)), fmaxf(fabsf(st[k].z), fabsf(st[k].w))));
-        // every A row under the power of two of ITS OWN maximum (the eight threads of a row: lanes t & 7): exact, and a
-        // row that is tiny next to its neighbours keeps its bits (a flushed reference row would mask all its samples)
-        m = fmaxf(m, dpp<0xB1>(m));      // quad_perm [1,0,3,2]
-        m = fmaxf(m, dpp<0x4E>(m));      // quad_perm [2,3,0,1]
-        m = fmaxf(m, dpp<0x141>(m));     // row_half_mirror: the other quad of the eight
-        float sa, sa_inv;
-        pow2_scale_of(m, sa, sa_inv);
-        if ((tid & 7) == 0) s_red[tid >> 3] = sa_inv;
-        // thread t holds channels 32 ks .. + 31 (ks = t & 7) of row t >> 3: channel 32 ks + 16 e + 4 kg + w -> fp16
-        // position 32 ks + 8 kg + 4 e + w (the k order of the B operand below)
-        char *hrow = s_hi + (tid >> 3) * kStageRow + (tid & 7) * 64, *lrow = s_lo + (tid >> 3) * kStageRow + (tid & 7) * 64;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const int e = k >> 2, kg = k & 3;
-            unsigned h0, l0, h1, l1;
-            split_f16_pair(st[k].x * sa, st[k].y * sa, h0, l0);
-            split_f16_pair(st[k].z * sa, st[k].w * sa, h1, l1);
-            typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-            *reinterpret_cast<u32x2_t *>(hrow + kg * 16 + e * 8) = u32x2_t{h0, h1};
-            *reinterpret_cast<u32x2_t *>(lrow + kg * 16 + e * 8) = u32x2_t{l0, l1};
-        }
-    }
-    __syncthreads();
-    const int ln = lane & 15, lk = lane >> 4;
-    f32x4 acc[PASSES][2][4];     // [pass][pixel half][row quarter]
-#pragma unroll
-    for (int q = 0; q < PASSES; ++q)
-#pragma unroll
-        for (int t = 0; t < 8; ++t) acc[q][t >> 2][t & 3] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float amax = 0.f;
-    const int paddr = (4 * ln + lk) * 4;
-    const char *ahp = s_hi + ln * kStageRow + lk * 16, *alp = s_lo + ln * kStageRow + lk * 16;
-#pragma unroll
-    for (int q = 0; q < PASSES; ++q) {
-        const int jb = 8 * q + 2 * wave;
-        if (jb >= nb) break;                                 // wave-uniform, forward exit
-        const bool has1 = jb + 1 < nb;
-        int offh[4];
-#pragma unroll
-        for (int hh = 0; hh < 4; ++hh)
-            offh[hh] = (hh < 2 || has1) ? s_rows[min(jb * 32 + hh * 16 + (lane >> 2), U - 1)] * kRowBytes + (lane & 3) * 16
-                                        : 0x7ffff000;                       // (no second block: zeros, no traffic)
-        constexpr int kSt = 2;
-        float4 b[kSt][4][2];
-#pragma unroll
-        for (int qq = 0; qq < kSt; ++qq)
-#pragma unroll
-            for (int hh = 0; hh < 4; ++hh)
-#pragma unroll
-                for (int e = 0; e < 2; ++e) b[qq][hh][e] = buf_load_f4(src, offh[hh] + qq * 128 + e * 64, 0);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-            f16x8 ahi[2], alo[2];
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {
-                ahi[g] = *reinterpret_cast<const f16x8 *>(ahp + g * 16 * kStageRow + ks * 64);
-                alo[g] = *reinterpret_cast<const f16x8 *>(alp + g * 16 * kStageRow + ks * 64);
-            }
-#pragma unroll
-            for (int hh = 0; hh < 4; ++hh) {
-                if (hh >= 2 && !has1) continue;              // wave-uniform
-                float v[8];
-#pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const float4 x = b[ks % kSt][hh][e];
-                    v[4 * e + 0] = __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(x.x))) * s_src;
-                    v[4 * e + 1] = __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(x.y))) * s_src;
-                    v[4 * e + 2] = __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(x.z))) * s_src;
-                    v[4 * e + 3] = __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(x.w))) * s_src;
-                }
-                f16x8 bhi, blo;
-                split_f16x8<true>(v, bhi, blo, amax);
-#pragma unroll
-                for (int g = 0; g < 2; ++g) {
-                    acc[q][g][hh] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo[g], bhi, acc[q][g][hh], 0, 0, 0);
-                    acc[q][g][hh] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[g], blo, acc[q][g][hh], 0, 0, 0);
-                    acc[q][g][hh] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[g], bhi, acc[q][g][hh], 0, 0, 0);
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (ks + kSt < 8) {
-#pragma unroll
-                for (int hh = 0; hh < 4; ++hh)
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) b[ks % kSt][hh][e] = buf_load_f4(src, offh[hh] + (ks + kSt) * 128 + e * 64, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    __syncthreads();  // every wave is done with the stage: the array may take the results
-    const f32x4 ai[2] = {*reinterpret_cast<const f32x4 *>(s_red + 4 * lk), *reinterpret_cast<const f32x4 *>(s_red + 16 + 4 * lk)};
-#pragma unroll
-    for (int q = 0; q < PASSES; ++q) {
-        const int jb = 8 * q + 2 * wave;
-        if (jb >= nb) break;
-        const bool has1 = jb + 1 < nb;
-        float *drow = s_D + (4 * lk) * STRIDE + jb * 32 + ln;
-#pragma unroll
-        for (int g = 0; g < 2; ++g)
-#pragma unroll
-            for (int hh = 0; hh < 4; ++hh) {
-                if (hh >= 2 && !has1) continue;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) drow[(16 * g + r) * STRIDE + 16 * hh] = (acc[q][g][hh][r] * ai[g][r]) * inv_src;
-            }
-    }
-    return !(amax < kF16GuardLimit);
-}
-
-// ---- the second GEMM of a tile (out_t = B . F2_U) as split-fp16 products ---------------------------------------------
-// B rows: finished in LDS by the soft-max phase, then (tile_convert_b_rows) scaled by 2^10 and split to fp16 hi | lo in
-// place per group of eight columns -- two plain 16-byte reads per fragment.  Needs attention x weights <= 1, i.e. the
-// soft-max on.  Source rows: quarter-row loads (a lane LOADS 16 bytes of row 16 ks + 8 lh + 4 s + q: four instructions of
-// 4 rows x 256 B per step), halves traded with lane ^ 16 (v_permlane16_swap), scaled by the per-pair estimate and split on
-// the register pairs the loads leave (the same rows passed the guard of the first GEMM).  Wave w: channels 64 w .. + 63.
-// The scheme of the warp-specialised kernel's G2 (kernels_forward_tile_ws.inc), inside the one-block-per-tile kernel.
-__device__ __forceinline__ void tile_convert_b_rows(float *row_a, float *row_b, int ucols, int lane)
-{
-    for (int g0 = 0; g0 < ucols / 8; g0 += 32) {
-        const int grp = g0 + (lane & 31);
-        if (grp >= ucols / 8) continue;
-        float *gp = (lane < 32 ? row_a : row_b) + grp * 8;
-        const float4 x0 = *reinterpret_cast<const float4 *>(gp), x1 = *reinterpret_cast<const float4 *>(gp + 4);
-        const float bv[8] = {x0.x * 1024.f, x0.y * 1024.f, x0.z * 1024.f, x0.w * 1024.f,
-                             x1.x * 1024.f, x1.y * 1024.f, x1.z * 1024.f, x1.w * 1024.f};
-        f16x8 bhi8, blo8;
-        float bdummy = 0.f;
-        split_f16x8<false>(bv, bhi8, blo8, bdummy);      // (values <= 2^10 by construction: soft-max on)
-        *reinterpret_cast<f16x8 *>(gp) = bhi8;
-        *reinterpret_cast<f16x8 *>(gp + 4) = blo8;
-    }
-}
-
-// A_F32 (the backward's d feat_ref = Bs . F2_U): the A rows are plain fp32 in LDS (any row stride) and are scaled by the
-// power of two s_a (the caller's exact block maximum -> [2^10, 2^11)) and split on the fly, eight values per k-step and lane.
-template <int STRIDE, bool A_F32 = false, class Store>
-__device__ __forceinline__ void tile_gemm_out_split(const float *srcp, unsigned map_bytes, const int *s_rows, const float *s_B,
-                                                    int upad, int wave, int lane, float s_src, float inv_src, Store &&store,
-                                                    float s_a = 1024.f)
-{
-    constexpr int kRowBytes = 1024, kD2 = 4;
-    const int li = lane & 31, lh = lane >> 5;
-    const int nks = upad >> 4;
-    const int c0 = wave * 64;
-    const int voff = (c0 + 4 * (lane & 15)) * 4;
-    float4 xring[kD2][4];
-    int ridx[4];
-    auto g2_rows = [&](int ks) {   // row indices of this lane's four loads of step ks (past the list: whatever LDS holds, never used)
-        const int4 a = *reinterpret_cast<const int4 *>(s_rows + min(ks, nks - 1) * 16 + (lane >> 4) * 4);
-        ridx[0] = a.x; ridx[1] = a.y; ridx[2] = a.z; ridx[3] = a.w;
-    };
-    if (nks == 0) {   // no source row in reach of the tile (every sample outside the image): out = 0, like the exact form
-        const int chan0 = c0 + 4 * (lane & 15) + 2 * ((lane >> 4) & 1);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) store((r & 3) + 8 * (r >> 2) + 4 * lh, chan0, f32x2{0.f, 0.f});
-        return;
-    }
-#pragma unroll
-    for (int ks = 0; ks < kD2; ++ks) {
-        g2_rows(ks);
-        unsigned nbytes = ks < nks ? map_bytes : 0u;
-        asm volatile("" : "+s"(nbytes));
-        const __amdgpu_buffer_rsrc_t srck = make_rsrc(srcp, nbytes);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) xring[ks][q] = buf_load_f4(srck, ridx[q] * kRowBytes + voff, 0);
-    }
-    g2_rows(kD2);
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.f;
-    const float *arow = s_B + li * STRIDE + lh * 8;
-    auto kstep = [&](int ks, float4 (&xr)[4]) {
-        f16x8 ahi, alo;
-        if constexpr (A_F32) {
-            float av[8], unused = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) av[e] = arow[ks * 16 + e] * s_a;
-            split_f16x8<false>(av, ahi, alo, unused);
-        } else {
-            ahi = *reinterpret_cast<const f16x8 *>(arow + ks * 16);
-            alo = *reinterpret_cast<const f16x8 *>(arow + ks * 16 + 4);
-        }
-        f32x2 v[8];
-        const f32x2 s2 = {s_src, s_src};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            auto r0 = __builtin_amdgcn_permlane16_swap(__float_as_uint(xr[q].x), __float_as_uint(xr[q].z), false, false);
-            auto r1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(xr[q].y), __float_as_uint(xr[q].w), false, false);
-            v[q] = f32x2{__uint_as_float(r0[0]), __uint_as_float(r1[0])} * s2;
-            v[4 + q] = f32x2{__uint_as_float(r0[1]), __uint_as_float(r1[1])} * s2;
-        }
-        f16x8 ehi, elo, ohi, olo;
-        split_f16x8_pairs(v, ehi, elo, ohi, olo);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(alo, ehi, acc0, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, elo, acc0, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, ehi, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(alo, ohi, acc1, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, olo, acc1, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi, ohi, acc1, 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        {
-            unsigned nbytes = ks + kD2 < nks ? map_bytes : 0u;
-            asm volatile("" : "+s"(nbytes));
-            const __amdgpu_buffer_rsrc_t srck = make_rsrc(srcp, nbytes);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) xr[q] = buf_load_f4(srck, ridx[q] * kRowBytes + voff, 0);
-        }
-        g2_rows(ks + kD2 + 1);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-#pragma unroll 1
-    for (int ks0 = 0; ks0 < nks; ks0 += kD2) {
-#pragma unroll
-        for (int q = 0; q < kD2; ++q)
-            if (ks0 + q < nks) kstep(ks0 + q, xring[q]);
-    }
-    // accumulator t, column n = 16 s + cq  <->  channel c0 + 4 cq + 2 s + t ; register r <-> pixel (r & 3) + 8 (r >> 2) + 4 lh
-    const float inv = inv_src * (1.f / s_a);            // (s_a: 2^10 for the pre-converted B rows of the forward)
-    const int chan = c0 + 4 * (lane & 15) + 2 * ((lane >> 4) & 1);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) store((r & 3) + 8 * (r >> 2) + 4 * lh, chan, f32x2{acc0[r] * inv, acc1[r] * inv});
+    return (size_t)(fwd_tile_array_floats(rows) + rows + kTilePix + 48 + kTilePix * 4) * 4 + (size_t)hw_words * 8 +
+           (kpl == 1 ? (size_t)kTilePix * kWave * 8 : 0);
 }
 
 // ---- the tile kernel -------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""The ordering in front of every tile kernel (tile_keys_kernel + tile_order_kernel, csrc/kernels_forward_tile.inc), read back
+"""The ordering in front of every tile kernel (tile_keys_kernel + tile_order_kernel, csrc/kernels_tile_order.inc), read back
 from the workspace the forward leaves (layout: csrc/et_tile_host.h / include/epipolar_amd.h):
 
   * `perm` of every pair is a permutation of the pair's reference pixels, padded with -1 to whole tiles;
@@ -9,8 +9,10 @@ from the workspace the forward leaves (layout: csrc/et_tile_host.h / include/epi
   * pixels without a segment come last.
 
 Shapes: the bench's 64 x 64 (4096 keys), 10 x 10 (100 pixels: a padded last tile, 128-key bitonic sort), 33 x 20 (non-square, 1024
-keys), 96 x 96 (16384-key bitonic sort: the full three-stage rounds); 256 .. 4096 keys take the radix sort (round 6) -- one shape per
-width of its counter scan, with and without padding keys.
+keys), 96 x 96 (16384-key bitonic sort: the full three-stage rounds).  Every key count takes the same bitonic network, whose
+merge step k = 2^s runs its s strides three per trip through LDS and the remainder (s mod 3) as one two-stage or one-stage trip:
+the key count decides which mix of rounds runs -- one shape each for 256, 512, 2048 and 4096 keys as well, with and without
+padding keys.
 """
 import math
 
@@ -45,7 +47,7 @@ def _regions(ws, n, h, w):
 
 
 @pytest.mark.parametrize("n,h,w,k", [(5, 64, 64, 64), (3, 10, 10, 16), (4, 33, 20, 20), (2, 96, 96, 64),
-                                     # (round 6: 256 .. 4096 keys take the radix sort -- every counter-scan width of it)
+                                     # (the bitonic network's round structure at 256, 512, 2048 and 4096 keys, padded and not)
                                      (3, 16, 16, 16), (3, 15, 15, 16), (3, 20, 20, 16), (2, 40, 40, 32), (2, 48, 64, 48)],
                          ids=["64x64", "10x10-padded-tile", "33x20", "96x96", "16x16-256-keys", "15x15-padded-256", "20x20-512-keys",
                               "40x40-2048-keys", "48x64-padded-4096"])
