@@ -202,7 +202,7 @@ int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, cons
         tp.ovf_list = w.ovf_list;
     }
     // capacity of the second launch's kernel: a deferred tile beyond it is shared by kDetHardParts blocks there (deterministic form)
-    tp.list_cap = (tile_rows(desc) == kTileRowsSmall && ET_BWD_LIST_MERGED) ? kTileRowsMergedLarge : tile_rows_cap(desc);
+    tp.list_cap = tile_rows(desc) == kTileRowsSmall ? kTileRowsMergedLarge : tile_rows_cap(desc);
     if (int e = launch_bwd_tile(tp, rows, kpl, det, dev, st)) return e;
     if (defer) {
         if (int e = check_launch("et_epipolar_backward_tiled(merged)")) return e;
@@ -212,13 +212,12 @@ int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, cons
         tp.ovf_count = nullptr;
         tp.rows_cap = tile_rows_cap(desc);
         int e;
-        if (tile_rows(desc) == kTileRowsSmall && ET_BWD_LIST_MERGED) {
+        if (tile_rows(desc) == kTileRowsSmall) {
             // round 6: the deferred tiles of a 64 x 64 map (193 .. ~280 rows) by the MERGED kernel of 288 columns -- one
-            // derivation of the samples' slots for both arrays, no half passes (a tile beyond 288 rows is split there)
+            // derivation of the samples' slots for both arrays, no half passes (a tile beyond 288 rows is split there);
+            // measured against the one-array kernel of 256 rows in profiles/r06_bwd_ab.txt
             tp.rows_cap = kTileRowsMergedLarge;
             e = launch_bwd_tile_list_as<kTileRowsMergedLarge>(tp, det, dev, st);
-        } else if (tile_rows(desc) == kTileRowsSmall) {
-            e = launch_bwd_tile_list_as<kTileRowsSmall>(tp, det, dev, st);
         } else {
             e = launch_bwd_tile_list_as<kTileRowsLarge>(tp, det, dev, st);
         }

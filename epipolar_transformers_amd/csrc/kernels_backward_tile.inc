@@ -84,26 +84,15 @@ struct BwdTileParams {
 constexpr int kDetGuardMask = 1 << 2;   // sticky error word, bit 2: a fixed-point contribution of the deterministic backward was out of range
 constexpr int kDetHardParts = 8;    // blocks of the second launch that share a deferred tile beyond that launch's own capacity
 
-#ifndef ET_BWD_ONE_ROUND_256
-#define ET_BWD_ONE_ROUND_256 1      // (development: 0 = two rounds of atomics in the 256-row one-array kernel, as until round 5)
-#endif
 #ifndef ET_BWD_NO_ATOMICS
 #define ET_BWD_NO_ATOMICS 0
 #endif
-#ifndef ET_BWD_MERGED_BLOCKS
-#define ET_BWD_MERGED_BLOCKS 3      // blocks per CU the 64 x 64 kernels are compiled for (development: -DET_BWD_MERGED_BLOCKS=2)
-#endif
-// Blocks of the merged launch that start during one pixel-group run of a split tile (~100 us beside the CU's other blocks;
-// the launch retires ~7 tiles per us with 192 columns at 64 x 64, ~5.3 with 288 at 96 x 96): see the over-capacity policy below.
-#ifndef ET_BWD_IN_PLACE_TILES
-#define ET_BWD_IN_PLACE_TILES 256
-#endif
-#ifndef ET_BWD_LIST_MERGED
-#define ET_BWD_LIST_MERGED 1        // (development: 0 = the second launch of a 64 x 64 call is the one-array kernel of 256 rows)
-#endif
+constexpr int kBwdMergedBlocks = 3;     // blocks per CU the 64 x 64 kernels are compiled for
 // over-capacity tiles of a merged launch that are still searched / split in place (the ring has a few dozen per call, the room rig
 // ~150); beyond that count the call is one of MANY such tiles and they go to the second launch without a search
-constexpr int kBwdInPlaceTiles = ET_BWD_IN_PLACE_TILES;
+constexpr int kBwdInPlaceTiles = 256;
+// Blocks of the merged launch that start during one pixel-group run of a split tile (~100 us beside the CU's other blocks;
+// the launch retires ~7 tiles per us with 192 columns at 64 x 64, ~5.3 with 288 at 96 x 96): see the over-capacity policy below.
 constexpr int bwd_blocks_per_group(int rows) { return rows == kTileRowsMergedLarge ? 550 : 700; }
 // one tile (`vb`: its index, pair-major) by one block -- or, in a short list of deferred tiles, by `nparts` blocks: pixel
 // groups are independent (grad_src is added with atomics, every other output is per pixel), so block `part` takes the
@@ -800,8 +789,8 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
             if (mask == 3) gemm_transposed(s_D, ref, s_D2, gout);
             else if (mask == 1) gemm_transposed(s_D, ref, nullptr, gout);
             else if (mask == 2) gemm_transposed(s_D2, gout, nullptr, gout);
-        } else if ((ROWS >= kTileRowsLarge || (ROWS == kTileRowsSmall && ET_BWD_ONE_ROUND_256)) && (d.src_grad_mask & 3) == 3) {
-            // ================= 4'. one round of atomics in the one-array kernels too (K > 64, large maps) =================
+        } else if ((d.src_grad_mask & 3) == 3) {
+            // ================= 4'. one round of atomics in the one-array kernels too (256, 384 and 512 rows) =================
             // (Round 6: the 256-row kernel as well -- it takes the tiles the merged kernel defers, every fifth one when the epipole
             //  lies inside the map.  The call is bound by the RATE of float atomics, 1.31 TB/s on this chip whatever their scope
             //  (scripts/micro/atomic_scopes.hip; bench.py extra.box.atomic_probe): 1 KB per (tile, row) and round.)
@@ -974,7 +963,7 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
 
 // The kernel: one tile per block (the launch covers every tile) ...
 template <int KPL, int ROWS, bool DET = false>
-__global__ __launch_bounds__(256, ((ROWS == kTileRowsSmall || ROWS == kTileRowsMerged) && KPL == 1) ? ET_BWD_MERGED_BLOCKS : 2) void epipolar_bwd_tile_kernel(const BwdTileParams tp)
+__global__ __launch_bounds__(256, ((ROWS == kTileRowsSmall || ROWS == kTileRowsMerged) && KPL == 1) ? kBwdMergedBlocks : 2) void epipolar_bwd_tile_kernel(const BwdTileParams tp)
 {
     bwd_tile_body<KPL, ROWS, DET>(tp, xcd_remap(blockIdx.x, tp.b.total_blocks));
 }

@@ -321,21 +321,9 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
     //   * Work split: 16-row UNITS dealt out round robin (wave w: units w, w + 4, w + 8, w + 12), each against both
     //     16-pixel halves of the tile.  With U ~ 165 that is 11 units: 3 + 3 + 3 + 2 (whole 32-row blocks gave
     //     2 + 2 + 1 + 1 blocks: two waves idle for a third of the phase).
-    //   * Round 6 experiment, OFF (-DET_WS_G1_VEC=n turns it on): the LAST units of a tile on VECTOR waves (g1v_issue / g1v_finish
-    //     below).  The vector waves wait 6-8.5 k cycles of every phase A for G1 (13 k on the matrix waves,
-    //     profiles/r06_ws_phase_cycles.txt); giving min(n, units - 4) units to vector waves 0, 1, .. leaves the matrix waves
-    //     2 + 2 + 1 + 1 units of ten instead of 3 + 3 + 2 + 2 -- and the call gets 4 % SLOWER at n = 2 and 4, 9 % at 6 and 8
-    //     (profiles/r06_fwd_ab.txt, call 11): G1's time is not one wave's latency chain but the CU's LDS pipe (640 ds_bpermute
-    //     + 320 fragment reads per tile, whoever issues them) beside the conversions' VALU slots.
-#ifndef ET_WS_G1_VEC
-#define ET_WS_G1_VEC 0
-#endif
-    constexpr int kG1VecMax = ET_WS_G1_VEC < NV ? ET_WS_G1_VEC : NV;
-    auto g1_matrix_units = [&](int U) {      // units 0 .. NM - 1 stay on the matrix waves, NM .. on vector waves 0 ..
-        const int n = (U + 15) >> 4;
-        return n - min(kG1VecMax, max(0, n - kWsMatrixWaves));
-    };
-    constexpr int kD1 = 6;       // ring depth in 32-channel k-steps
+    //   * Round 6 tried the LAST units of a tile on the vector waves, which wait for G1 in every phase A: the call got 4-9 %
+    //     slower, because G1 is bound by the CU's LDS pipe whoever issues its work (profiles/r06_fwd_ab.txt, call 11).
+    constexpr int kD1 = 6;      // ring depth in 32-channel k-steps
     constexpr int kUnits = (ROWS + 63) / 64;          // units per wave at most
     float4 bring[kD1][2];        // [flat k-step mod kD1][segment e]
     int boff[kUnits];
@@ -346,7 +334,7 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
         for (int ui = 0; ui < kUnits; ++ui) {
             const int unit = wave + 4 * ui;
             boff[ui] = kOob;
-            if (U > 0 && unit < g1_matrix_units(U))
+            if (U > 0 && unit < ((U + 15) >> 4))
                 boff[ui] = s_rows[slot * ROWS + min(unit * 16 + (lane >> 2), U - 1)] * kRowBytes + (lane & 3) * 16;
         }
         const int n = valid ? tile_of(j) / tp.tiles_per_pair : 0;
@@ -365,7 +353,7 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
         const __amdgpu_buffer_rsrc_t src = make_rsrc(p.fsrc + (size_t)n * HW * C, map_bytes);
         const float s_src = tp.scales[n * 4 + 2];
         const float inv = tp.scales[n * 4 + 3];          // 1 / s_src; the A rows carry their own scales (s_ainv)
-        const int nunits = g1_matrix_units(U);           // (the units behind them: vector waves, g1v_finish)
+        const int nunits = (U + 15) >> 4;                // 16-row units of the tile
         if (wave >= nunits) return;
         float *dst = s_arr + (j & 1) * kArr;
         float amax = 0.f;
@@ -469,105 +457,6 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
                 tp.ovf_list[atomicAdd(tp.ovf_count, 1)] = tile_of(j);
         }
     };
-    // ---- G1 units on the vector waves: unit g1_matrix_units(U) + vw of T_j by vector wave vw, while the matrix waves run the
-    // first units of the same tile.  The same arithmetic as g1_main (one unit = 16 source rows x 32 pixels x 256 channels: 16 loads
-    // of 16 B per lane, 64 ds_bpermute, 48 MFMAs), a ring of its own four k-steps deep whose first fill goes out at the START of
-    // the phase (g1v_issue: its latency passes behind S1 / S2 / the copy), the rest behind them (g1v_finish). ----
-    constexpr int kDV = 8;          // (the whole unit: k-steps 0-3 go out at the start of the phase, 4-7 behind S1 -- no refill in the k-loop)
-    float4 vring[kDV][2];
-    int vboff = kOob, g1v_unit = -1;
-    auto g1v_issue = [&](int j, bool valid) {
-        const int slot = valid ? j % kWsSlots : 0;
-        const int U = valid ? s_U[slot] : 0;
-        const int nm = U > 0 ? g1_matrix_units(U) : 0;
-        const int unit = nm + (wave - kWsMatrixWaves);
-        const bool have = kG1VecMax > 0 && U > 0 && unit * 16 < U;
-        g1v_unit = have ? unit : -1;
-        vboff = have ? s_rows[slot * ROWS + min(unit * 16 + (lane >> 2), U - 1)] * kRowBytes + (lane & 3) * 16 : kOob;
-        const int n = valid ? tile_of(j) / tp.tiles_per_pair : 0;
-        const __amdgpu_buffer_rsrc_t src = make_rsrc(p.fsrc + (size_t)n * HW * C, have ? map_bytes : 0u);
-#pragma unroll
-        for (int ks = 0; ks < kDV / 2; ++ks)
-#pragma unroll
-            for (int e = 0; e < 2; ++e) vring[ks][e] = buf_load_f4(src, vboff + ks * 128 + e * 64, 0);
-    };
-    auto g1v_issue2 = [&](int j, bool valid) {       // (behind S1: its registers are free again)
-        const int n = valid ? tile_of(j) / tp.tiles_per_pair : 0;
-        const __amdgpu_buffer_rsrc_t src = make_rsrc(p.fsrc + (size_t)n * HW * C, g1v_unit >= 0 ? map_bytes : 0u);
-#pragma unroll
-        for (int ks = kDV / 2; ks < kDV; ++ks)
-#pragma unroll
-            for (int e = 0; e < 2; ++e) vring[ks][e] = buf_load_f4(src, vboff + ks * 128 + e * 64, 0);
-    };
-    auto g1v_finish = [&](int j) {
-        if (g1v_unit < 0) return;
-        const int slot = j % kWsSlots;
-        const int n = tile_of(j) / tp.tiles_per_pair;
-        const __amdgpu_buffer_rsrc_t src = make_rsrc(p.fsrc + (size_t)n * HW * C, map_bytes);
-        const float s_src = tp.scales[n * 4 + 2];
-        const float inv = tp.scales[n * 4 + 3];
-        float *dst = s_arr + (j & 1) * kArr;
-        int lane_o = lane;          // (lane-dependent addresses from an opaque copy: not hoisted out of the tile loop and spilled)
-        asm volatile("" : "+v"(lane_o));
-        const int paddr = (4 * (lane_o & 15) + (lane_o >> 4)) * 4;
-        const char *ahp = s_ahi + astage_of(j) * kAStageBytes + (lane_o & 15) * kWsAStageRow + (lane_o >> 4) * 16;
-        const char *alp = s_alo + astage_of(j) * kAStageBytes + (lane_o & 15) * kWsAStageRow + (lane_o >> 4) * 16;
-        f32x4 acc[2];
-        acc[0] = acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-        float dummy = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-            f16x8 ahi[2], alo[2];
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {
-                ahi[g] = *reinterpret_cast<const f16x8 *>(ahp + g * 16 * kWsAStageRow + ks * 64);
-                alo[g] = *reinterpret_cast<const f16x8 *>(alp + g * 16 * kWsAStageRow + ks * 64);
-            }
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const float4 x = vring[ks % kDV][e];
-                const f32x2 s2 = {s_src, s_src};
-                const f32x2 p0 = f32x2{__int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(x.x))),
-                                       __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(x.y)))} * s2;
-                const f32x2 p1 = f32x2{__int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(x.z))),
-                                       __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(x.w)))} * s2;
-                v[4 * e + 0] = p0.x;
-                v[4 * e + 1] = p0.y;
-                v[4 * e + 2] = p1.x;
-                v[4 * e + 3] = p1.y;
-            }
-            f16x8 bhi, blo;
-            split_f16x8<false>(v, bhi, blo, dummy);
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {
-                acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo[g], bhi, acc[g], 0, 0, 0);
-                acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[g], blo, acc[g], 0, 0, 0);
-                acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi[g], bhi, acc[g], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (ks + kDV < 8) {
-#pragma unroll
-                for (int e = 0; e < 2; ++e) vring[ks % kDV][e] = buf_load_f4(src, vboff + (ks + kDV) * 128 + e * 64, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        float *drow = dst + (4 * (lane_o >> 4)) * STRIDE + g1v_unit * 16 + (lane_o & 15);
-        const f32x4 ai0 = *reinterpret_cast<const f32x4 *>(s_ainv + astage_of(j) * kTilePix + 4 * (lane_o >> 4));
-        const f32x4 ai1 = *reinterpret_cast<const f32x4 *>(s_ainv + astage_of(j) * kTilePix + 16 + 4 * (lane_o >> 4));
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            drow[r * STRIDE] = (acc[0][r] * ai0[r]) * inv;
-            drow[(16 + r) * STRIDE] = (acc[1][r] * ai1[r]) * inv;
-        }
-        // (the fp16 guard on the results, as in g1_main)
-        const float amax = ((fabsf(acc[0][0]) + fabsf(acc[0][1])) + (fabsf(acc[0][2]) + fabsf(acc[0][3]))) +
-                           ((fabsf(acc[1][0]) + fabsf(acc[1][1])) + (fabsf(acc[1][2]) + fabsf(acc[1][3])));
-        if (__builtin_amdgcn_ballot_w64(!(amax < kF16ResultGuard)) != 0 && lane == 0) {
-            if (atomicExch(&s_U[slot], -1) >= 0 && (KH == 1 || atomicExch(&s_dead[seq_of(j) & 3], 1) == 0))
-                tp.ovf_list[atomicAdd(tp.ovf_count, 1)] = tile_of(j);
-        }
-    };
     // The reference rows of T_jc (1 KB per pixel, read once), on the VECTOR waves (the matrix waves are the critical
     // path of both phases): wave vw takes pixels PW vw .. + PW - 1, a lane four channels.  The loads are issued at the
     // start of phase B, ahead of SM -- the pixel ids come straight from the tile list through the constant address
@@ -579,12 +468,9 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
     //  1.07 vs 1.00 ms -- and in phase A on the vector waves, which wait 5-7 k cycles there, with a second A stage in place of
     //  the sample table (locations recomputed in SM): 1.03 vs 1.00 ms; profiles/r04_fwd_ab.txt.  The waits are not free time:
     //  the LDS pipe and the SIMDs are shared, and moving work between the phases moves the contention with it.)
-#ifndef ET_WS_COPY_IN_A
-#define ET_WS_COPY_IN_A 1
-#endif
     // Round 6: the copy of T_{i+1} runs in phase A(i) (loads ahead of S1, conversion behind S2), where the vector waves used to wait
     // 4-6 k cycles for G1, instead of in phase B(i) behind SM, where they are the critical path (profiles/r06_fwd_ab.txt).
-    constexpr bool kCopyInA = ET_WS_COPY_IN_A != 0 && KH == 1;     // (KH == 2: one stage -- behind the second half's SM, once per tile)
+    constexpr bool kCopyInA = (KH == 1);     // (KH == 2: one stage -- behind the second half's SM, once per tile)
     constexpr int kCopyPix = kTilePix / NV;
     float4 crow[kCopyPix];
     int cpx[kCopyPix];
@@ -793,14 +679,11 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
             // feat rows loaded behind the loop to make room for three or four: 1-2 % slower, profiles/r04_fwd_ab.txt) is filled BEFORE
             // the barrier and the staging of the out tile: one weight-fetch latency of sixteen off the chain (-0.9 %, r05_fwd_ab.txt)
             const __amdgpu_buffer_rsrc_t r_w = make_rsrc(tp.packed_w, (unsigned)kRgPackedWords * 4u);
-#ifndef ET_G3_RING
-#define ET_G3_RING 4
-#endif
             // Round 6: FOUR k-steps deep.  A weight fetch takes ~600 cycles from L2 and a k-step 6 MFMAs = 192: two deep, every
             // k-step waited ~200 cycles for its fragments -- 3 k of the ~7.6 k cycles G3 adds to a tile.  The registers come from
             // the feat rows: they are loaded LATE, at k-steps 12 and 13, into what the ring no longer refills (behind the loop
             // their latency was exposed whole: 1-2 % slower in round 4; before the loop they cost the ring its depth).
-            constexpr int kRing3 = ET_G3_RING;
+            constexpr int kRing3 = 4;
             u32x4 bq[kRing3][4];      // [k-step mod kRing3][2 nb + term]
             const int woff = (wave * 2) * 2 * 1024 + lane * 16;     // fragment (ks, nb = 2 wave, hi) of this lane, bytes
             auto wload = [&](int ks, u32x4 (&dst)[4]) {
@@ -834,15 +717,10 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
                 const int pix = s_pix[slot * kTilePix + m];
                 return pix >= 0 ? pix * kRowBytes + (c0 + li3) * 4 : kOob;
             };
-            constexpr bool kLateFeat = kRing3 > 2;
-            auto feat_load = [&](int nb) {
+            auto feat_load = [&](int nb) {      // (late, inside the k-loop below: see kRing3)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) fr[nb][r] = buf_load_f1_nt(refb, xoff_of(r) + nb * 128, 0);      // (padding pixel: zeros)
             };
-            if (!kLateFeat) {
-                feat_load(0);
-                feat_load(1);
-            }
             const float bias0 = tp.bias[c0 + li], bias1 = tp.bias[c0 + 32 + li];
             const float unscale = tp.scales[n * 4 + 3] * reinterpret_cast<const float *>(tp.packed_w)[kRgPackedWords];
             f32x16 g0, g1;
@@ -866,8 +744,8 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
                 g1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, __builtin_bit_cast(f16x8, bb[2]), g1, 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if (ks + kRing3 < 16) wload(ks + kRing3, bq[ks % kRing3]);
-                else if (kLateFeat && ks == 16 - kRing3) feat_load(0);
-                else if (kLateFeat && ks == 17 - kRing3) feat_load(1);
+                else if (ks == 16 - kRing3) feat_load(0);
+                else if (ks == 17 - kRing3) feat_load(1);
                 __builtin_amdgcn_sched_barrier(0);
             }
             const __amdgpu_buffer_rsrc_t xb = make_rsrc(tp.x + (size_t)n * HW * C, map_bytes);
@@ -1429,10 +1307,6 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
             ET_WS_STAMP(4);
         }
     } else {
-#ifdef ET_WS_VPRIO
-        // (experiment: the second-dispatched half of the vector waves loses the VALU arbitration to the older half on every SIMD)
-        if (vw >= NV / 2) __builtin_amdgcn_s_setprio(ET_WS_VPRIO);
-#endif
         int vb_target = 0;
         s1_prefetch(0, true);
         const bool drawer = vw == 0 && lane == 0;
@@ -1440,13 +1314,11 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
         for (int i = -1;; ++i) {
             if (i >= 1 && !has_tile(i - 1)) break;
             if (KH == 1 || (i & 1) == 0) draw_issue(drawer);       // the tile of step i + 3 (committed at the end of phase B)
-            if (kG1VecMax > 0) g1v_issue(i, has_tile(i));          // this wave's unit of G1(T_i), if the tile has one for it
             if (kCopyInA) copy_load(i + 1, has_tile(i + 1));
 #ifdef ET_WS_PROFILE
             if (!(tp.setprio & 32))
 #endif
             if (has_tile(i + 1)) s1(i + 1);
-            if (kG1VecMax > 0) g1v_issue2(i, has_tile(i));
             s1_prefetch(i + 2, has_tile(i + 2));
             ET_WS_STAMP(1);
             vb_target += NV;
@@ -1455,7 +1327,6 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
             if (last && has_tile(i + 1)) s2(i + 1);
             ET_WS_STAMP(3);
             if (kCopyInA) copy_finish(i + 1, has_tile(i + 1));
-            if (kG1VecMax > 0) g1v_finish(i);
             lds_barrier();
             ET_WS_STAMP(4);
 #ifdef ET_WS_PROFILE

@@ -1,6 +1,6 @@
 """Development: dump the tile ordering (perm of every pair) of a few shapes to an .npz -- run once per library build
-(EPIPOLAR_AMD_LIB) and compare the files: the radix sort (round 6) must give the bitonic network's permutation bit for bit
-(keys are unique).    python scripts/dev/order_perm_dump.py OUT.npz    |    python scripts/dev/order_perm_dump.py --compare A.npz B.npz"""
+(EPIPOLAR_AMD_LIB) and compare the files: a changed ordering kernel must give the bitonic network's permutation bit for bit
+(keys are unique).  python scripts/dev/order_perm_dump.py OUT.npz    |    python scripts/dev/order_perm_dump.py --compare A.npz B.npz"""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))

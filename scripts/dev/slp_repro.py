@@ -1,4 +1,4 @@
-"""Development: the parked split-fp16 one-block-per-tile forward (scripts/dev/classic_split_fp16.diff) built with and without
+"""Development: the split-fp16 one-block-per-tile forward (ET_VARIANT_TILE_CLASSIC; scripts/dev/README.md) built with and without
 SLP vectorisation -- does the intermittent fault follow the packed-fp32 instructions of the tap arithmetic?"""
 import sys, torch
 sys.path.insert(0, ".")
