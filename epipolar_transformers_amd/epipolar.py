@@ -77,37 +77,10 @@ class _TrainEpilogue(torch.autograd.Function):
          bias = (bz - mean) gamma / sigma + beta -- the same kernel the eval path runs.
     Backward (`ops.z_backward`): one pass over g and the saved y for the batch norm's two sums, then the same GEMM kernel
     once more -- it forms the batch norm's input gradient dy on the fly, writes it and returns d out = dy . Wz + g; only the
-    weight gradient dy^T out goes to the library (the convolution's wgrad).  Measured at Config 2 (profiles/r05_train_epilogue.txt)
-    against the alternatives kept behind two development switches: aten's own batch-norm / convolution backward on the 4-D
-    tensors (slower than autograd's stock path on channels-last memory) and plain 2-D torch ops (`_backward_rows`: the tall
-    dy^T out GEMM takes 18 ms in rocBLAS)."""
-
-    ATEN_BACKWARD = False     # development switches (scripts/train_epilogue_time.py): aten's 4-D backward ops ...
-    ROWS_BACKWARD = False     # ... or plain 2-D torch ops, instead of the et_z_backward kernels
-    LIBRARY_WGRAD = False     # ... the library's 1x1 convolution wgrad instead of et_z_wgrad
-
-    @staticmethod
-    def _backward_rows(g4, o4, y4, zw, gamma, mean, invstd, zresidual, need_out):
-        """d out, d Wz, d bz, d gamma, d beta of x = gamma (y - mean) invstd + beta [+ out], y = out Wz^T + bz, over rows."""
-        c = o4.shape[-1]
-        g, o, y = g4.reshape(-1, c), o4.reshape(-1, c), y4.reshape(-1, c)
-        m = g.shape[0]
-        dbeta = g.sum(0)
-        gy = torch.einsum("mc,mc->c", g, y)
-        dgamma = (gy - mean * dbeta) * invstd                    # sum g yhat,  yhat = (y - mean) invstd
-        k = gamma * invstd
-        # dy = k (g - dbeta / m - yhat dgamma / m)  =  a g + b y + c0   per channel
-        b = -k * dgamma * invstd / m
-        c0 = k * (mean * invstd * dgamma - dbeta) / m
-        dy = torch.addcmul(c0, y, b).addcmul_(g, k)
-        w2 = zw.reshape(c, c)
-        dzw = (dy.t() @ o).reshape(zw.shape)
-        dzb = dy.sum(0)
-        dout = None
-        if need_out:
-            dout = (torch.addmm(g, dy, w2) if zresidual else dy @ w2).view(o4.shape)
-        return dout, dzw, dzb, dgamma, dbeta
-
+    weight gradient dy^T out is a kernel of its own (`ops.z_wgrad`).  Measured at Config 2 (profiles/r05_train_epilogue.txt)
+    against aten's own batch-norm / convolution backward on the 4-D tensors (slower than autograd's stock path on channels-last
+    memory), plain 2-D torch ops (the tall dy^T out GEMM takes 18 ms in rocBLAS) and the library's 1x1 convolution wgrad in
+    place of et_z_wgrad: this form was the fastest."""
 
     @staticmethod
     def forward(ctx, out, feat, zw, zb, gamma, beta, eps, zresidual):
@@ -131,34 +104,14 @@ class _TrainEpilogue(torch.autograd.Function):
     def backward(ctx, gx, _gm, _gv):
         o, y, zw, gamma, mean, invstd = ctx.saved_tensors
         g = gx.contiguous(memory_format=torch.channels_last)
-        if not (_TrainEpilogue.ATEN_BACKWARD or _TrainEpilogue.ROWS_BACKWARD):
-            # et_z_backward: the batch norm's sums (one pass over g and y), then ONE GEMM kernel that forms dy on the fly, writes
-            # it, and returns d out = dy . Wz + g; the weight gradient dy^T out is the library's convolution wgrad
-            c = o.shape[-1]
-            dout, dy, dgamma, dbeta = ops.z_backward(g.permute(0, 2, 3, 1), y, mean, invstd, gamma.detach().contiguous(),
-                                                     ops.residual_gemm_pack(zw.detach().reshape(c, c).t().contiguous()), ctx.zresidual)
-            if _TrainEpilogue.LIBRARY_WGRAD:
-                _, dzw, dzb = torch.ops.aten.convolution_backward(dy.permute(0, 3, 1, 2), o.permute(0, 3, 1, 2), zw, [c], [1, 1], [0, 0],
-                                                                 [1, 1], False, [0, 0], 1, [False, True, True])
-            else:
-                dzw, dzb = ops.z_wgrad(dy, o)
-                dzw = dzw.view(zw.shape)
-            return (dout.permute(0, 3, 1, 2) if ctx.needs_input_grad[0] else None, g if ctx.has_feat and ctx.needs_input_grad[1] else None,
-                    dzw, dzb, dgamma, dbeta, None, None)
-        if not _TrainEpilogue.ATEN_BACKWARD:
-            dout, dzw, dzb, dgamma, dbeta = _TrainEpilogue._backward_rows(g.permute(0, 2, 3, 1), o, y, zw, gamma, mean, invstd,
-                                                                          ctx.zresidual, bool(ctx.needs_input_grad[0]))
-            return (dout.permute(0, 3, 1, 2) if dout is not None else None, g if ctx.has_feat and ctx.needs_input_grad[1] else None,
-                    dzw, dzb, dgamma, dbeta, None, None)
-        dy, dgamma, dbeta = torch.ops.aten.native_batch_norm_backward(
-            g, y.permute(0, 3, 1, 2), gamma, None, None, mean, invstd, True, ctx.eps, [True, True, True])
-        dout, dzw, dzb = torch.ops.aten.convolution_backward(
-            dy, o.permute(0, 3, 1, 2), zw, [zw.shape[0]], [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
-            [bool(ctx.needs_input_grad[0]), True, True])
-        if ctx.needs_input_grad[0] and ctx.zresidual:
-            dout = dout + g
-        return (dout if ctx.needs_input_grad[0] else None, g if ctx.has_feat and ctx.needs_input_grad[1] else None,
-                dzw, dzb, dgamma, dbeta, None, None)
+        # et_z_backward: the batch norm's sums (one pass over g and y), then ONE GEMM kernel that forms dy on the fly, writes
+        # it, and returns d out = dy . Wz + g; et_z_wgrad contracts dy^T out over the rows
+        c = o.shape[-1]
+        dout, dy, dgamma, dbeta = ops.z_backward(g.permute(0, 2, 3, 1), y, mean, invstd, gamma.detach().contiguous(),
+                                                 ops.residual_gemm_pack(zw.detach().reshape(c, c).t().contiguous()), ctx.zresidual)
+        dzw, dzb = ops.z_wgrad(dy, o)
+        return (dout.permute(0, 3, 1, 2) if ctx.needs_input_grad[0] else None, g if ctx.has_feat and ctx.needs_input_grad[1] else None,
+                dzw.view(zw.shape), dzb, dgamma, dbeta, None, None)
 
 
 class Epipolar(nn.Module):
@@ -273,6 +226,50 @@ class Epipolar(nn.Module):
         c_sim = 3 if e.FIND_CORR == "rgb" else feat1.shape[1] // (e.BOTTLENECK if "theta" in e.PARAMETERIZED else 1)
         return c_sim <= 512
 
+    def _maps(self, feat1, feat2, ref1=None, ref2=None, value_only=False):
+        """(q, m1, m2) of epipolar.py:131-153: the query map, the map the similarity samples and the map the output sums, after
+        the OTHER_GRAD detaches and theta / phi / g.  m1 IS m2 (one object) where the reference samples one tensor for both.
+        `value_only`: (None, None, m2) -- the supplied-depth route reads no similarity."""
+        e = self.cfg.EPIPOLAR
+        q = m1 = None
+        if value_only:                                                                  # (no query, nothing sampled for a similarity)
+            pass
+        elif e.FIND_CORR == "rgb":                                                      # :131-136
+            assert ref1 is not None and ref2 is not None
+            assert "other1" not in e.OTHER_GRAD and "phi" not in e.PARAMETERIZED
+            m1, q = ref2.detach(), ref1
+        else:
+            other1 = feat2 if "other1" in e.OTHER_GRAD else feat2.detach()              # :138-141
+            m1 = self.phi(other1) if "phi" in e.PARAMETERIZED else other1               # :142-143
+            q = self.theta(feat1) if "theta" in e.PARAMETERIZED else feat1              # :144-145
+        other2 = feat2 if "other2" in e.OTHER_GRAD else feat2.detach()                  # :147-150
+        m2 = self.g(other2) if "g" in e.PARAMETERIZED else other2                       # :152-153
+        return q, m1, m2
+
+    def _sample_torch(self, src, locs):
+        """The torch restatement's sampler (epipolar.py:199 / :210, + POOLING :200-202): one grid_sample of `src` (N,C,H,W) for
+        all K samples of `locs` (K,N,H,W,2) -> (N,K',C,H,W)."""
+        K, H, W = self.sample_size, self.feat_h, self.feat_w
+        N, c = src.shape[0], src.shape[1]
+        grid = locs.permute(1, 0, 2, 3, 4).reshape(N, K * H, W, 2)
+        s_ = F.grid_sample(src, grid, mode="bilinear", padding_mode="zeros",
+                           align_corners=bool(amd_knob(self.cfg, "ALIGN_CORNERS", False)))
+        s_ = s_.view(N, c, K, H, W).permute(0, 2, 1, 3, 4)
+        if self.cfg.EPIPOLAR.POOLING:
+            s_ = s_.reshape(N, 2, K // 2, c, H, W).max(1)[0]                  # view(stride, K // stride, ...).max(0)
+        return s_
+
+    def _corr_pos_torch(self, locs, idx):
+        """The torch restatement's corr_pos (epipolar.py:225-231 / :237-242): the location of sample `idx` (N,H,W) of every
+        pixel, de-normalised to feature-map pixels (multiview.py:39-57, either convention)."""
+        H, W = self.feat_h, self.feat_w
+        N = idx.shape[0]
+        with torch.no_grad():
+            pos = torch.gather(locs.permute(1, 0, 2, 3, 4), 1, idx.view(N, 1, H, W, 1).expand(-1, -1, -1, -1, 2)).squeeze(1)
+            if self.cfg.EPIPOLAR.USE_CORRECT_NORMALIZE:
+                return torch.stack([(pos[..., 0] + 1) * (W - 1) / 2, (pos[..., 1] + 1) * (H - 1) / 2], -1)
+            return torch.stack([(pos[..., 0] + 1) * W / 2 - 0.5, (pos[..., 1] + 1) * H / 2 - 0.5], -1)
+
     def _attend_with_depth(self, feat1, feat2, P1, P2, depth):
         """An externally supplied `depth` (epipolar.py:101-104, 217-218): the given (N,K',H,W) weights REPLACE the similarity
         -- no mask, no soft-max --, `out` is their weighted sum of the (pooled) samples of other2 (ATTENTION avg, :243) or the
@@ -283,8 +280,7 @@ class Epipolar(nn.Module):
         rows = self.sample_size // 2 if e.POOLING else self.sample_size
         if w.dim() != 4 or w.shape[0] != feat2.shape[0] or w.shape[1] != rows or tuple(w.shape[2:]) != (self.feat_h, self.feat_w):
             raise ValueError("depth must be (N, %d, %d, %d) weights, got %s" % (rows, self.feat_h, self.feat_w, tuple(w.shape)))
-        other2 = feat2 if "other2" in e.OTHER_GRAD else feat2.detach()                  # :147-150
-        m2 = self.g(other2) if "g" in e.PARAMETERIZED else other2                       # :152-153
+        m2 = self._maps(feat1, feat2, value_only=True)[2]
         with torch.no_grad():
             cam = self._cam(P1, P2, feat2.device)
         w = w.to(feat2)
@@ -300,48 +296,33 @@ class Epipolar(nn.Module):
                                                    w.contiguous(), mode)
         return out, w, corr_pos
 
+    def _weigh_torch(self, s2, sim, locs):
+        """(out, corr_pos) of the torch restatement from the sampled value map `s2` (N,K',C,H,W) and the weights `sim`
+        (N,K',H,W): epipolar.py:225-243."""
+        N, H, W = s2.shape[0], self.feat_h, self.feat_w
+        idx = sim.argmax(1)                                                   # (N,H,W)   :225 / :237
+        corr_pos = self._corr_pos_torch(locs, idx)
+        if self.cfg.EPIPOLAR.ATTENTION == "max":                              # :232-235
+            out = torch.gather(s2, 1, idx.view(N, 1, 1, H, W).expand(-1, -1, s2.shape[2], -1, -1)).squeeze(1)
+        else:
+            out = (s2 * sim.unsqueeze(2)).sum(1)                              # :243
+        return out, corr_pos
+
     def _attend_with_depth_torch(self, m2, w, cam):
         """The supplied-depth branch as torch ops (epipolar.py:199-213, 225-243 with `sim` = the given weights): the route of
         shapes the general kernel does not take.  `cam`: the per-pair algebra, computed once by the caller."""
         _warn_slow_path(self.cfg)
-        e = self.cfg.EPIPOLAR
-        K, H, W = self.sample_size, self.feat_h, self.feat_w
-        N, c = m2.shape[0], m2.shape[1]
         with torch.no_grad():
             locs = ops.sample_locs(self.layer_spec(), cam)                    # (K,N,H,W,2)
-        grid = locs.permute(1, 0, 2, 3, 4).reshape(N, K * H, W, 2)
-        s2 = F.grid_sample(m2, grid, mode="bilinear", padding_mode="zeros",
-                           align_corners=bool(amd_knob(self.cfg, "ALIGN_CORNERS", False))).view(N, c, K, H, W).permute(0, 2, 1, 3, 4)
-        if e.POOLING:
-            s2 = s2.reshape(N, 2, K // 2, c, H, W).max(1)[0]
-        idx = w.argmax(1)
-        with torch.no_grad():
-            pos = torch.gather(locs.permute(1, 0, 2, 3, 4), 1, idx.view(N, 1, H, W, 1).expand(-1, -1, -1, -1, 2)).squeeze(1)
-            if e.USE_CORRECT_NORMALIZE:
-                corr_pos = torch.stack([(pos[..., 0] + 1) * (W - 1) / 2, (pos[..., 1] + 1) * (H - 1) / 2], -1)
-            else:
-                corr_pos = torch.stack([(pos[..., 0] + 1) * W / 2 - 0.5, (pos[..., 1] + 1) * H / 2 - 0.5], -1)
-        if e.ATTENTION == "max":
-            out = torch.gather(s2, 1, idx.view(N, 1, 1, H, W).expand(-1, -1, c, -1, -1)).squeeze(1)
-        else:
-            out = (s2 * w.unsqueeze(2)).sum(1)
+        out, corr_pos = self._weigh_torch(self._sample_torch(m2, locs), w, locs)
         return out, w, corr_pos
 
     def _attend_general_hip(self, feat1, feat2, P1, P2, camera=None, other_camera=None, ref1=None, ref2=None):
         """The non-headline branches through the HIP general kernels: the 1x1 convolutions act on the maps
         (epipolar.py:138-153: torch / MIOpen GEMMs, with autograd), the kernel samples, pools, masks, soft-maxes and sums
-        without materialising a K x C x H x W tensor (`ops.GeneralAttend`; prior / cosine / ATTENTION max:
-        `ops.forward_general_nhwc`, forward only)."""
+        without materialising a K x C x H x W tensor (`ops.GeneralAttend`, forward and backward)."""
         e = self.cfg.EPIPOLAR
-        if e.FIND_CORR == "rgb":                                                        # :131-136
-            assert "other1" not in e.OTHER_GRAD and "phi" not in e.PARAMETERIZED
-            m1, q = ref2.detach(), ref1
-        else:
-            other1 = feat2 if "other1" in e.OTHER_GRAD else feat2.detach()              # :138-141
-            m1 = self.phi(other1) if "phi" in e.PARAMETERIZED else other1               # :142-143
-            q = self.theta(feat1) if "theta" in e.PARAMETERIZED else feat1              # :144-145
-        other2 = feat2 if "other2" in e.OTHER_GRAD else feat2.detach()                  # :147-150
-        m2 = self.g(other2) if "g" in e.PARAMETERIZED else other2                       # :152-153
+        q, m1, m2 = self._maps(feat1, feat2, ref1, ref2)
         with torch.no_grad():
             cam = self._cam(P1, P2, feat2.device)
         is_max = e.ATTENTION == "max"
@@ -361,36 +342,12 @@ class Epipolar(nn.Module):
         epipolar_similarity (:272-321) as batched GPU torch ops (autograd included).  Returns (out, attn, corr_pos)
         like `attend`; `out` is what the reference stacks at :247 (before z)."""
         e = self.cfg.EPIPOLAR
-        K, H, W = self.sample_size, self.feat_h, self.feat_w
-        if e.FIND_CORR == "rgb":                                              # epipolar.py:131-136
-            assert ref1 is not None and ref2 is not None
-            assert "other1" not in e.OTHER_GRAD and "phi" not in e.PARAMETERIZED
-            other1, q = ref2.detach(), ref1
-        else:
-            other1 = feat2 if "other1" in e.OTHER_GRAD else feat2.detach()    # :138-141
-            if "phi" in e.PARAMETERIZED:
-                other1 = self.phi(other1)                                     # :142-143
-            q = self.theta(feat1) if "theta" in e.PARAMETERIZED else feat1    # :144-145
-        other2 = feat2 if "other2" in e.OTHER_GRAD else feat2.detach()        # :147-150
-        if "g" in e.PARAMETERIZED:
-            other2 = self.g(other2)                                           # :152-153
-        N = feat2.shape[0]
+        q, other1, other2 = self._maps(feat1, feat2, ref1, ref2)
         with torch.no_grad():
             cam = self._cam(P1, P2, feat2.device)
             locs = ops.sample_locs(self.layer_spec(), cam)                    # (K,N,H,W,2): the HIP geometry kernel
-        align = bool(amd_knob(self.cfg, "ALIGN_CORNERS", False))
-
-        def sample(src):                                                      # :199 / :210, + POOLING :200-202
-            c = src.shape[1]
-            grid = locs.permute(1, 0, 2, 3, 4).reshape(N, K * H, W, 2)        # one grid_sample per map for all K samples
-            s_ = F.grid_sample(src, grid, mode="bilinear", padding_mode="zeros", align_corners=align)
-            s_ = s_.view(N, c, K, H, W).permute(0, 2, 1, 3, 4)                # (N,K,C,H,W)
-            if e.POOLING:
-                s_ = s_.reshape(N, 2, K // 2, c, H, W).max(1)[0]              # view(stride, K // stride, ...).max(0)
-            return s_
-
-        s1 = sample(other1)
-        s2 = s1 if other1 is other2 else sample(other2)
+        s1 = self._sample_torch(other1, locs)
+        s2 = s1 if other1 is other2 else self._sample_torch(other2, locs)
         Ks = s1.shape[1]
         qe = q.unsqueeze(1)
         if e.ATTENTION == "max":                                              # :282-286: always cosine, no mask / soft-max
@@ -415,19 +372,7 @@ class Epipolar(nn.Module):
                         sim = sim * pr                                        # :308-309
                 else:
                     sim = sim / Ks                                            # :310-311
-        idx = sim.argmax(1)                                                   # (N,H,W)   :225 / :237
-        with torch.no_grad():
-            gl = locs.permute(1, 0, 2, 3, 4)                                  # (N,K,H,W,2)
-            pos = torch.gather(gl, 1, idx.view(N, 1, H, W, 1).expand(-1, -1, -1, -1, 2)).squeeze(1)
-            if self.cfg.EPIPOLAR.USE_CORRECT_NORMALIZE:                       # multiview.py:39-57
-                corr_pos = torch.stack([(pos[..., 0] + 1) * (W - 1) / 2, (pos[..., 1] + 1) * (H - 1) / 2], -1)
-            else:
-                corr_pos = torch.stack([(pos[..., 0] + 1) * W / 2 - 0.5, (pos[..., 1] + 1) * H / 2 - 0.5], -1)
-        if e.ATTENTION == "max":                                              # :232-235
-            c2 = s2.shape[2]
-            out = torch.gather(s2, 1, idx.view(N, 1, 1, H, W).expand(-1, -1, c2, -1, -1)).squeeze(1)
-        else:
-            out = (s2 * sim.unsqueeze(2)).sum(1)                              # :243
+        out, corr_pos = self._weigh_torch(s2, sim, locs)
         return out, sim, corr_pos
 
     # ------------------------------------------------------------ debug geometry
@@ -580,12 +525,7 @@ class Epipolar(nn.Module):
         self._check_mode(depth, ref1, ref2)
         if depth is not None:
             out, attn, corr_pos = self._attend_with_depth(feat1, feat2, P1, P2, depth)
-            sample_locs = None
-            if self.debug or self.cfg.VIS.EPIPOLAR_LINE:
-                sample_locs = ops.sample_locs(self.layer_spec(), self._cam(P1, P2, feat2.device))
-            if self.debug:
-                return (out, corr_pos, attn, sample_locs) + self._debug_geometry(self._cam(P1, P2, feat2.device))
-            return out, corr_pos, attn, (sample_locs.transpose(0, 1) if sample_locs is not None else None)
+            return self._result(out, corr_pos, attn, P1, P2, feat2.device)
         fused = self._fused_mode(ref1, ref2)
         if fused:
             out, attn, corr_pos = self.attend(feat1, feat2, P1, P2)
@@ -601,15 +541,19 @@ class Epipolar(nn.Module):
                 finalout = torch.addmm(bf, o.reshape(-1, o.shape[-1]), wt).view_as(o).permute(0, 3, 1, 2)
         else:
             finalout, _ = self._epilogue_torch(out)
-        sample_locs = None
+        return self._result(finalout, corr_pos, attn, P1, P2, feat1.device)
+
+    def _result(self, finalout, corr_pos, attn, P1, P2, device):
+        """What forward() returns: the reference's 4-tuple -- its last entry the sample locations (N,K,H,W,2) with
+        VIS.EPIPOLAR_LINE (epipolar.py:267), else None -- or, with debug=True, the 9-tuple of the visualisers (:264-265):
+        sample_locs untransposed (K,N,H,W,2) + the geometry."""
+        if not (self.debug or self.cfg.VIS.EPIPOLAR_LINE):
+            return finalout, corr_pos, attn, None
+        cam = self._cam(P1, P2, device)
+        locs = ops.sample_locs(self.layer_spec(), cam)
         if self.debug:
-            # epipolar.py:264-265: the 9-tuple of the visualisers -- sample_locs untransposed (K,N,H,W,2) + the geometry
-            cam = self._cam(P1, P2, feat1.device)
-            return (finalout, corr_pos, attn, ops.sample_locs(self.layer_spec(), cam)) + self._debug_geometry(cam)
-        if self.cfg.VIS.EPIPOLAR_LINE:
-            cam = self._cam(P1, P2, feat1.device)
-            sample_locs = ops.sample_locs(self.layer_spec(), cam).transpose(0, 1)   # (K,N,H,W,2) -> epipolar.py:267
-        return finalout, corr_pos, attn, sample_locs
+            return (finalout, corr_pos, attn, locs) + self._debug_geometry(cam)
+        return finalout, corr_pos, attn, locs.transpose(0, 1)
 
     def forward_fused(self, feat1, feat2, P1, P2, camera=None, other_camera=None):
         """forward + `ret + feat` (resnet.py:388).  In eval mode the whole epilogue is ONE GEMM, x = feat + bf + out @ Wf^T:

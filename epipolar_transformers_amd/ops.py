@@ -69,16 +69,58 @@ class LayerSpec:
             variant=int(self.variant) & ~_lib.ET_VARIANT_BWD_DETERMINISTIC)
 
 
-def _require_gpu(t: torch.Tensor, name: str):
+def _require_gpu(t: torch.Tensor, name: str, dtype=torch.float32):
     if not t.is_cuda:
         raise _lib.EpipolarAmdError(
             "%s is on %s: the epipolar hot path runs on the GPU only (no CPU fallback)" % (name, t.device))
-    if t.dtype != torch.float32:
-        raise TypeError("%s must be float32, got %s" % (name, t.dtype))
+    if t.dtype != dtype:
+        raise TypeError("%s must be %s, got %s" % (name, str(dtype).replace("torch.", ""), t.dtype))
+
+
+# The argument checks of every wrapper: the library takes raw addresses, so whatever it is to read or write is checked HERE for
+# device, dtype, shape and contiguity (EpipolarAmdError off the GPU, TypeError for the dtype, ValueError for the rest), with
+# raised errors -- `python -O` must not remove them.  `msg`: the ValueError's text where a wrapper has words of its own.
+def _require_f32(t: torch.Tensor, name: str, device, shape=None, msg: str = None):
+    """`t`: a contiguous float32 tensor on `device` (a GPU) -- of `shape` where one is given; (..., 256) fixes the last
+    dimension only."""
+    _require_gpu(t, name)
+    ok = t.device == device and t.is_contiguous()
+    if ok and shape is not None:
+        ok = tuple(t.shape[-1:]) == tuple(shape[1:]) if shape[0] is Ellipsis else tuple(t.shape) == tuple(shape)
+    if not ok:
+        raise ValueError(msg or "%s must be a contiguous float32 tensor%s on %s, got %s on %s" % (
+            name, "" if shape is None else " of shape %s" % (tuple(shape),), device, tuple(t.shape), t.device))
+
+
+def _require_vector(t: torch.Tensor, name: str, n: int, device):
+    """`t`: `n` contiguous float32 values on `device` (a per-channel vector, whatever its number of dimensions)."""
+    _require_gpu(t, name)
+    if t.numel() != n or not t.is_contiguous() or t.device != device:
+        raise ValueError("%s must be a contiguous float32 vector of %d values on %s" % (name, n, device))
+
+
+def _require_bytes(t: torch.Tensor, name: str, nbytes: int, device, msg: str = None):
+    """`t`: a contiguous uint8 buffer of at least `nbytes` bytes on `device` (a workspace, a packed weight)."""
+    _require_gpu(t, name, torch.uint8)
+    if t.numel() < nbytes or not t.is_contiguous() or t.device != device:
+        raise ValueError(msg or "%s must be a contiguous uint8 tensor of at least %d bytes on %s" % (name, nbytes, device))
+
+
+def _require_cam(cam: torch.Tensor, n: int, device):
+    _require_f32(cam, "cam", device, (n, _lib.ET_CAM_STRIDE), "cam must be a contiguous (N,%d) tensor" % _lib.ET_CAM_STRIDE)
 
 
 def _stream(t: torch.Tensor):
     return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _call(name: str, on, *args):
+    """Call the library's export `name` with the device of `on` (a tensor or a device) current, and raise its error under that
+    name.  `on` None: the caller holds the device guard itself (it has more to do under it)."""
+    if on is None:
+        return _lib.check(getattr(_lib.load(), name)(*args), name)
+    with torch.cuda.device(on.device if isinstance(on, torch.Tensor) else on):
+        _lib.check(getattr(_lib.load(), name)(*args), name)
 
 
 POISON_OUTPUTS = False      # tests set this: every output buffer starts as NaN, so that a kernel that leaves part of its
@@ -108,8 +150,7 @@ def to_nhwc(x: torch.Tensor) -> torch.Tensor:
         return perm
     src = x.contiguous()
     dst = _empty((n, h, w, c), device=x.device, dtype=x.dtype)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().et_nchw_to_nhwc(n, c, h, w, _ptr(src), _ptr(dst), _stream(x)), "et_nchw_to_nhwc")
+    _call("et_nchw_to_nhwc", x, n, c, h, w, _ptr(src), _ptr(dst), _stream(x))
     return dst
 
 
@@ -118,22 +159,18 @@ def to_nchw_contiguous(x_nhwc: torch.Tensor) -> torch.Tensor:
     _require_gpu(x_nhwc, "feature map")
     n, h, w, c = x_nhwc.shape
     dst = _empty((n, c, h, w), device=x_nhwc.device, dtype=x_nhwc.dtype)
-    with torch.cuda.device(x_nhwc.device):
-        _lib.check(_lib.load().et_nhwc_to_nchw(n, c, h, w, _ptr(x_nhwc.contiguous()), _ptr(dst), _stream(x_nhwc)),
-                   "et_nhwc_to_nchw")
+    _call("et_nhwc_to_nchw", x_nhwc, n, c, h, w, _ptr(x_nhwc.contiguous()), _ptr(dst), _stream(x_nhwc))
     return dst
 
 
 def sample_locs(spec: LayerSpec, cam: torch.Tensor) -> torch.Tensor:
     """grid2sample_locs (epipolar.py:323-418): (K,N,H,W,2)."""
-    _require_gpu(cam, "cam")
+    _require_cam(cam, cam.shape[0], cam.device)
     n = cam.shape[0]
     xs, ys, steps = spec.constants(cam.device)
     out = _empty((spec.K, n, spec.H, spec.W, 2), device=cam.device)
     d = spec.desc(n, 4)
-    with torch.cuda.device(cam.device):
-        _lib.check(_lib.load().et_sample_locs(ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(out),
-                                              _stream(cam)), "et_sample_locs")
+    _call("et_sample_locs", cam, ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(out), _stream(cam))
     return out
 
 
@@ -143,39 +180,37 @@ def _general_flags(pooling=False, prior_mul=False, cosine=False, attention_max=F
             (_lib.ET_GENERAL_SIM_PRIOR if sim_prior else 0))
 
 
+def _require_general(spec: LayerSpec, q, map_sim, map_val, cam, prior, pooling):
+    """The arguments forward_general_nhwc and backward_general_nhwc share.  Returns (n, h, w, cs, cv, K')."""
+    for t, nm in ((q, "q"), (map_sim, "map_sim"), (map_val, "map_val")):
+        _require_f32(t, nm, q.device, msg="q / map_sim / map_val must be contiguous (N,H,W,C) tensors")
+    n, h, w, cs = q.shape
+    if (h, w) != (spec.H, spec.W) or map_sim.shape != q.shape or map_val.dim() != 4 or map_val.shape[:3] != q.shape[:3]:
+        raise ValueError("maps %s / %s / %s do not match the layer's %dx%d" %
+                         (tuple(q.shape), tuple(map_sim.shape), tuple(map_val.shape), spec.H, spec.W))
+    _require_cam(cam, n, q.device)
+    ks = spec.K // 2 if pooling else spec.K
+    if prior is not None:
+        _require_f32(prior, "prior", q.device, (n, ks, h, w),
+                     "prior must be (N,K',H,W) = %s, got %s" % ((n, ks, h, w), tuple(prior.shape)))
+    return n, h, w, cs, map_val.shape[-1], ks
+
+
 def forward_general_nhwc(spec: LayerSpec, q: torch.Tensor, map_sim: torch.Tensor, map_val: torch.Tensor, cam: torch.Tensor,
                          prior: torch.Tensor = None, pooling=False, prior_mul=False, cosine=False, attention_max=False,
                          want_attn=True, want_corr=True, sim_prior=False):
     """The operator's parameterised / pooled / prior branches as ONE kernel (et_epipolar_forward_general; forward only).
     q, map_sim: (N,H,W,Cs); map_val: (N,H,W,Cv), channels last, contiguous; prior: (N,K',H,W) or None, K' = K/2 with
     `pooling` (epipolar.py:200-202), else K.  Returns out (N,H,W,Cv), attn (N,K',H,W)|None, corr_pos (N,H,W,2)|None."""
-    for t, nm in ((q, "q"), (map_sim, "map_sim"), (map_val, "map_val"), (cam, "cam")):
-        _require_gpu(t, nm)
-    n, h, w, cs = q.shape
-    cv = map_val.shape[-1]
-    if (h, w) != (spec.H, spec.W) or map_sim.shape != q.shape or map_val.shape[:3] != q.shape[:3]:
-        raise ValueError("maps %s / %s / %s do not match the layer's %dx%d" %
-                         (tuple(q.shape), tuple(map_sim.shape), tuple(map_val.shape), spec.H, spec.W))
-    if cam.shape != (n, _lib.ET_CAM_STRIDE) or not cam.is_contiguous():
-        raise ValueError("cam must be a contiguous (N,%d) tensor" % _lib.ET_CAM_STRIDE)
-    if not (q.is_contiguous() and map_sim.is_contiguous() and map_val.is_contiguous()):
-        raise ValueError("q / map_sim / map_val must be contiguous (N,H,W,C) tensors")
-    ks = spec.K // 2 if pooling else spec.K
-    if prior is not None:
-        _require_gpu(prior, "prior")
-        if tuple(prior.shape) != (n, ks, h, w) or not prior.is_contiguous():
-            raise ValueError("prior must be (N,K',H,W) = %s, got %s" % ((n, ks, h, w), tuple(prior.shape)))
+    n, h, w, cs, cv, ks = _require_general(spec, q, map_sim, map_val, cam, prior, pooling)
     xs, ys, steps = spec.constants(q.device)
     out = _empty((n, h, w, cv), device=q.device)
     attn = _empty((n, ks, h, w), device=q.device) if want_attn else None
     corr = _empty((n, h, w, 2), device=q.device) if want_corr else None
     flags = _general_flags(pooling, prior_mul, cosine, attention_max, sim_prior)
     d = spec.desc(n, 4)
-    with torch.cuda.device(q.device):
-        _lib.check(_lib.load().et_epipolar_forward_general(
-            ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(q), _ptr(map_sim), _ptr(map_val),
-            _ptr(prior) if prior is not None else None, cs, cv, flags, _ptr(out), _ptr(attn) if want_attn else None,
-            _ptr(corr) if want_corr else None, _stream(q)), "et_epipolar_forward_general")
+    _call("et_epipolar_forward_general", q, ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(q), _ptr(map_sim),
+          _ptr(map_val), _ptr(prior), cs, cv, flags, _ptr(out), _ptr(attn), _ptr(corr), _stream(q))
     return out, attn, corr
 
 
@@ -184,19 +219,8 @@ def backward_general_nhwc(spec: LayerSpec, q, map_sim, map_val, cam, grad_out, p
     """Backward of forward_general_nhwc, every branch: returns (grad_q, grad_map_sim | None, grad_map_val | None,
     grad_prior | None), NHWC maps, grad_prior (N,K',H,W).  The map gradients are accumulated with float atomics
     (reproducible to rounding only)."""
-    for t, nm in ((q, "q"), (map_sim, "map_sim"), (map_val, "map_val"), (cam, "cam"), (grad_out, "grad_out")):
-        _require_gpu(t, nm)
-    n, h, w, cs = q.shape
-    cv = map_val.shape[-1]
-    if tuple(grad_out.shape) != (n, h, w, cv) or not grad_out.is_contiguous():
-        raise ValueError("grad_out must be a contiguous (N,H,W,Cv) tensor")
-    if not (q.is_contiguous() and map_sim.is_contiguous() and map_val.is_contiguous()):
-        raise ValueError("q / map_sim / map_val must be contiguous (N,H,W,C) tensors")
-    ks = spec.K // 2 if pooling else spec.K
-    if prior is not None:
-        _require_gpu(prior, "prior")
-        if tuple(prior.shape) != (n, ks, h, w) or not prior.is_contiguous():
-            raise ValueError("prior must be (N,K',H,W) = %s, got %s" % ((n, ks, h, w), tuple(prior.shape)))
+    n, h, w, cs, cv, ks = _require_general(spec, q, map_sim, map_val, cam, prior, pooling)
+    _require_f32(grad_out, "grad_out", q.device, (n, h, w, cv), "grad_out must be a contiguous (N,H,W,Cv) tensor")
     xs, ys, steps = spec.constants(q.device)
     gq = _empty(None, like=q)
     gsim = torch.zeros_like(map_sim) if need_sim else None
@@ -204,11 +228,8 @@ def backward_general_nhwc(spec: LayerSpec, q, map_sim, map_val, cam, grad_out, p
     gprior = _empty(None, like=prior) if (need_prior and prior is not None) else None
     d = spec.desc(n, 4)
     flags = _general_flags(pooling, prior_mul, cosine, attention_max, sim_prior)
-    with torch.cuda.device(q.device):
-        _lib.check(_lib.load().et_epipolar_backward_general(
-            ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(q), _ptr(map_sim), _ptr(map_val),
-            _ptr(prior), _ptr(grad_out), cs, cv, flags, _ptr(gq), _ptr(gsim), _ptr(gval), _ptr(gprior),
-            _stream(q)), "et_epipolar_backward_general")
+    _call("et_epipolar_backward_general", q, ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(q), _ptr(map_sim),
+          _ptr(map_val), _ptr(prior), _ptr(grad_out), cs, cv, flags, _ptr(gq), _ptr(gsim), _ptr(gval), _ptr(gprior), _stream(q))
     return gq, gsim, gval, gprior
 
 
@@ -248,50 +269,49 @@ _TILE_BITS = (_lib.ET_VARIANT_TILE_SPLIT | _lib.ET_VARIANT_TILE_CLASSIC |
               _lib.ET_VARIANT_WS_SETPRIO | _lib.ET_VARIANT_TILE_EXACT | _lib.ET_VARIANT_WS_BAND | _lib.ET_VARIANT_BWD_SPLIT_IN_PLACE)   # bits that tune the tile path instead of leaving it
 
 
+def _require_pair(spec: LayerSpec, ref, src, cam, c: int = None):
+    """feat_ref / feat_src / cam of the headline entry points: contiguous (N,H,W,C) maps of the layer's size (with `c` channels,
+    where the kernel is written for one width) and their (N,27) algebra, on one GPU.  Returns (n, h, w, c)."""
+    for t, nm in ((ref, "feat_ref"), (src, "feat_src")):
+        _require_f32(t, nm, ref.device, msg="feat_ref / feat_src must be contiguous (N,H,W,C) tensors")
+    n, h, w, ch = ref.shape
+    if (h, w) != (spec.H, spec.W) or src.shape != ref.shape or (c is not None and ch != c):
+        raise ValueError("feature maps %s / %s do not match the layer's %dx%d%s" %
+                         (tuple(ref.shape), tuple(src.shape), spec.H, spec.W, "" if c is None else " x %d" % c))
+    _require_cam(cam, n, ref.device)
+    return n, h, w, ch
+
+
 def forward_nhwc(spec: LayerSpec, ref: torch.Tensor, src: torch.Tensor, cam: torch.Tensor,
                  want_attn=True, want_corr=True, res_bias=None, want_res_base=False, workspace=None):
     """ref/src: (N,H,W,C) contiguous.  Returns out (N,H,W,C), attn (N,K,H,W)|None, corr_pos (N,H,W,2)|None
     [, res_base (N,H,W,C) = ref + res_bias when want_res_base].  `workspace`: a caller-owned uint8 tensor for the
     tile path (see tile_workspace / tile_stats) instead of the cached per-(device, stream) one."""
-    for t, nm in ((ref, "feat_ref"), (src, "feat_src"), (cam, "cam")):
-        _require_gpu(t, nm)
-    n, h, w, c = ref.shape
-    if (h, w) != (spec.H, spec.W) or src.shape != ref.shape:
-        raise ValueError("feature maps %s / %s do not match the layer's %dx%d" %
-                         (tuple(ref.shape), tuple(src.shape), spec.H, spec.W))
-    if cam.shape != (n, _lib.ET_CAM_STRIDE) or not cam.is_contiguous():
-        raise ValueError("cam must be a contiguous (N,%d) tensor" % _lib.ET_CAM_STRIDE)
-    assert ref.is_contiguous() and src.is_contiguous()
+    n, h, w, c = _require_pair(spec, ref, src, cam)
+    if res_bias is not None:
+        if not want_res_base:
+            raise ValueError("res_bias is added into res_base: it needs want_res_base")
+        _require_vector(res_bias, "res_bias", c, ref.device)
     xs, ys, steps = spec.constants(ref.device)
     out = _empty(None, like=ref)
     attn = _empty((n, spec.K, h, w), device=ref.device) if want_attn else None
     corr = _empty((n, h, w, 2), device=ref.device) if want_corr else None
     base = _empty(None, like=ref) if want_res_base else None
-    if res_bias is not None:
-        assert want_res_base and res_bias.is_cuda and res_bias.numel() == c and res_bias.is_contiguous()
     d = spec.desc(n, c)
-    lib = _lib.load()
     # variant 0 (the library default) takes the MFMA tile formulation wherever it applies (C == 256 head);
     # any explicit variant bit selects the per-pixel kernels
-    ws_bytes = int(lib.et_epipolar_forward_workspace_bytes(ctypes.byref(d))) \
-        if (d.variant & ~_TILE_BITS) == 0 else 0
-    with torch.cuda.device(ref.device):
-        if ws_bytes > 0:
-            ws = workspace if workspace is not None else _workspace(ref.device, ws_bytes, "fwd")
-            if ws.numel() < ws_bytes or ws.device != ref.device:
-                raise ValueError("workspace of %d bytes on %s: need %d on %s" % (ws.numel(), ws.device, ws_bytes, ref.device))
-            _lib.check(lib.et_epipolar_forward_tiled(ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam),
-                                                     _ptr(ref), _ptr(src), _ptr(out), _ptr(attn), _ptr(corr),
-                                                     _ptr(res_bias), _ptr(base), _ptr(ws), ctypes.c_size_t(ws_bytes),
-                                                     _stream(ref)),
-                       "et_epipolar_forward_tiled")
-            if POISON_OUTPUTS:          # (test suite: surface a device-side fault at the call that caused it)
-                check_tile_errors(workspace=ws)
-        else:
-            _lib.check(lib.et_epipolar_forward(ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam),
-                                               _ptr(ref), _ptr(src), _ptr(out), _ptr(attn), _ptr(corr),
-                                               _ptr(res_bias), _ptr(base), _stream(ref)),
-                       "et_epipolar_forward")
+    ws_bytes = int(_lib.load().et_epipolar_forward_workspace_bytes(ctypes.byref(d))) if (d.variant & ~_TILE_BITS) == 0 else 0
+    args = (ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(ref), _ptr(src), _ptr(out), _ptr(attn), _ptr(corr),
+            _ptr(res_bias), _ptr(base))
+    if ws_bytes > 0:
+        ws = workspace if workspace is not None else _workspace(ref.device, ws_bytes, "fwd")
+        _require_bytes(ws, "workspace", ws_bytes, ref.device,
+                       "workspace of %d bytes on %s: need %d on %s" % (ws.numel(), ws.device, ws_bytes, ref.device))
+        _call("et_epipolar_forward_tiled", ref, *args, _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(ref))
+        if POISON_OUTPUTS:          # (test suite: surface a device-side fault at the call that caused it)
+            check_tile_errors(workspace=ws)
+    else:
+        _call("et_epipolar_forward", ref, *args, _stream(ref))
     if want_res_base:
         return out, attn, corr, base
     return out, attn, corr
@@ -312,25 +332,14 @@ def forward_fused_nhwc(spec: LayerSpec, ref: torch.Tensor, src: torch.Tensor, ca
                        bias: torch.Tensor, want_attn=True, want_corr=True, want_out=False, workspace=None):
     """The eval-mode layer as one data kernel (et_epipolar_forward_fused): returns x = ref + bias + out @ Wf^T (N,H,W,C),
     attn (N,K,H,W)|None, corr_pos (N,H,W,2)|None [, out when want_out].  `packed`: residual_gemm_pack(Wf)."""
-    for t, nm in ((ref, "feat_ref"), (src, "feat_src"), (cam, "cam"), (bias, "bias")):
-        _require_gpu(t, nm)
-    if not packed.is_cuda or packed.dtype != torch.uint8:
-        raise TypeError("packed must be the uint8 device buffer residual_gemm_pack returns")
-    n, h, w, c = ref.shape
-    if (h, w) != (spec.H, spec.W) or src.shape != ref.shape or c != 256:
-        raise ValueError("feature maps %s / %s do not match the layer's %dx%d x 256" % (tuple(ref.shape), tuple(src.shape), spec.H, spec.W))
-    if cam.shape != (n, _lib.ET_CAM_STRIDE) or not cam.is_contiguous():
-        raise ValueError("cam must be a contiguous (N,%d) tensor" % _lib.ET_CAM_STRIDE)
-    need = int(_lib.load().et_residual_gemm_packed_bytes())
-    if packed.numel() < need or not packed.is_contiguous() or packed.device != ref.device:
-        raise ValueError("packed holds %d bytes on %s: the kernel reads %d on %s (ops.residual_gemm_pack)" %
-                         (packed.numel(), packed.device, need, ref.device))
-    if not (ref.is_contiguous() and src.is_contiguous()):
-        raise ValueError("feat_ref / feat_src must be contiguous (N,H,W,C) tensors")
-    if bias.numel() != c or not bias.is_contiguous() or bias.device != ref.device:
-        raise ValueError("bias must be a contiguous float32 vector of %d values on %s" % (c, ref.device))
-    if workspace is not None and (workspace.device != ref.device or workspace.dtype != torch.uint8):
-        raise ValueError("workspace must be a uint8 tensor on %s" % (ref.device,))
+    n, h, w, c = _require_pair(spec, ref, src, cam, c=256)
+    lib = _lib.load()
+    need = int(lib.et_residual_gemm_packed_bytes())
+    _require_bytes(packed, "packed", need, ref.device, "packed holds %d bytes on %s: the kernel reads %d on %s (ops.residual_gemm_pack)" %
+                   (packed.numel(), packed.device, need, ref.device))
+    _require_vector(bias, "bias", c, ref.device)
+    if workspace is not None:
+        _require_bytes(workspace, "workspace", 0, ref.device, "workspace must be a uint8 tensor on %s" % (ref.device,))
     xs, ys, steps = spec.constants(ref.device)
     x = _empty(None, like=ref)
     # `out`: requested -> a fresh tensor; otherwise scratch for the rows of overflow tiles only (normally none is written),
@@ -339,14 +348,12 @@ def forward_fused_nhwc(spec: LayerSpec, ref: torch.Tensor, src: torch.Tensor, ca
     attn = _empty((n, spec.K, h, w), device=ref.device) if want_attn else None
     corr = _empty((n, h, w, 2), device=ref.device) if want_corr else None
     d = spec.desc(n, c)
-    lib = _lib.load()
     ws_bytes = int(lib.et_epipolar_forward_workspace_bytes(ctypes.byref(d)))
-    with torch.cuda.device(ref.device):
+    with torch.cuda.device(ref.device):             # (held here: the poll asks about the CURRENT device's stream)
         ws = workspace if workspace is not None else _workspace(ref.device, max(ws_bytes, 1), "fwd")
-        _lib.check(lib.et_epipolar_forward_fused(ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(ref),
-                                                 _ptr(src), _ptr(packed), _ptr(bias), _ptr(x), _ptr(attn), _ptr(corr),
-                                                 _ptr(out), 1 if want_out else 0, _ptr(ws), ctypes.c_size_t(ws.numel()),
-                                                 _stream(ref)), "et_epipolar_forward_fused")
+        _call("et_epipolar_forward_fused", None, ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(ref), _ptr(src),
+              _ptr(packed), _ptr(bias), _ptr(x), _ptr(attn), _ptr(corr), _ptr(out), 1 if want_out else 0, _ptr(ws),
+              ctypes.c_size_t(ws.numel()), _stream(ref))
         if POISON_OUTPUTS:
             check_tile_errors(workspace=ws)
         else:
@@ -398,17 +405,30 @@ def _own_workspace(workspace, nbytes: int, device, tag: str):
     """The caller-owned workspace, checked -- or, when the caller gave none, the cached buffer of `tag`."""
     if workspace is None:
         return _workspace(device, nbytes, tag)
-    if workspace.dtype != torch.uint8 or workspace.device != device or not workspace.is_contiguous() or workspace.numel() < nbytes:
-        raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, device))
+    _require_bytes(workspace, "workspace", nbytes, device)
     return workspace
 
 
-_TILE_ERROR_OFFSET = 4      # bytes: word 1 of the workspace header (et_epipolar_forward_workspace_error_offset: shape-independent)
+# The 64-word int32 header at the 256-byte-aligned base of a tile workspace (include/epipolar_amd.h, csrc/et_tile_host.h), read
+# HERE and nowhere else in the binding.  The words it uses:
+_HEADER_WORDS = 64
+_HEADER_DEFERRED = 0        # overflow / deferred count of the last tile call
+_HEADER_ERROR = 1           # the sticky error word (et_epipolar_forward_workspace_error_offset: 4 bytes in, whatever the shape)
+_HEADER_DIAGNOSTICS = 8     # words 0..7: what backward_deferred_tiles(header=True) returns
+
+
+def _aligned_base(buf: torch.Tensor) -> int:
+    return (-buf.data_ptr()) % 256                        # the library aligns the base up to 256 bytes
+
+
+def _header(buf: torch.Tensor) -> torch.Tensor:
+    """The header of the workspace `buf` as an int32 view (no copy, no synchronisation)."""
+    base = _aligned_base(buf)
+    return buf[base: base + 4 * _HEADER_WORDS].view(torch.int32)
 
 
 def _read_tile_error(buf: torch.Tensor) -> int:
-    base = (-buf.data_ptr()) % 256                        # the library aligns the base up to 256 bytes
-    return int(buf[base + _TILE_ERROR_OFFSET: base + _TILE_ERROR_OFFSET + 4].view(torch.int32).item())
+    return int(_header(buf)[_HEADER_ERROR].item())
 
 
 _TILE_ERROR_TEXT = ("the tile kernels reported device-side error bits 0x%x (bit 1: a matrix wave of et_epipolar_forward_fused gave "
@@ -418,8 +438,7 @@ _TILE_ERROR_TEXT = ("the tile kernels reported device-side error bits 0x%x (bit 
 
 
 def _clear_tile_error(buf: torch.Tensor):
-    base = (-buf.data_ptr()) % 256
-    buf[base + _TILE_ERROR_OFFSET: base + _TILE_ERROR_OFFSET + 4].zero_()
+    _header(buf)[_HEADER_ERROR:_HEADER_ERROR + 1].zero_()
 
 
 def check_tile_errors(spec: "LayerSpec" = None, n: int = None, c: int = 256, workspace: torch.Tensor = None, reset: bool = True):
@@ -487,10 +506,9 @@ def _poll_tile_error(buf: torch.Tensor):
     st.calls += 1
     if st.event is None and st.calls >= _TILE_ERROR_POLL_EVERY:
         st.calls = 0
-        base = (-buf.data_ptr()) % 256
         if st.host is None:
             st.host = torch.empty(1, dtype=torch.int32).pin_memory()
-        st.host.copy_(buf[base + _TILE_ERROR_OFFSET: base + _TILE_ERROR_OFFSET + 4].view(torch.int32), non_blocking=True)
+        st.host.copy_(_header(buf)[_HEADER_ERROR:_HEADER_ERROR + 1], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(buf.device))
         st.event = ev
@@ -515,10 +533,9 @@ def tile_stats(spec: LayerSpec, n: int, c: int, workspace: torch.Tensor) -> torc
     """Per-tile statistics the tile forward leaves in its workspace: int32 (N * tiles_per_pair,),
     U | groups << 16 (size of the tile's source-row set, number of pixel groups it was split into)."""
     d = spec.desc(n, c)
-    off = int(_lib.load().et_epipolar_forward_workspace_stats_offset(ctypes.byref(d)))
+    off = _aligned_base(workspace) + int(_lib.load().et_epipolar_forward_workspace_stats_offset(ctypes.byref(d)))
     tiles = n * ((spec.H * spec.W + 31) // 32)
-    base = (-workspace.data_ptr()) % 256                     # the library aligns the base up to 256 bytes
-    return workspace[base + off: base + off + 4 * tiles].view(torch.int32)
+    return workspace[off: off + 4 * tiles].view(torch.int32)
 
 
 _BWD_EXPLICIT = _lib.ET_VARIANT_BWD_ATOMIC | _lib.ET_VARIANT_BWD_UNSORTED | _lib.ET_VARIANT_NO_TILE
@@ -532,6 +549,18 @@ def det_tile_workspace(spec: LayerSpec, n: int, c: int, device) -> torch.Tensor:
                        device=device)
 
 
+def _default_backward_form(spec: LayerSpec, tile_bytes: int, use_workspace: bool) -> str:
+    """backward_nhwc's choice when the caller names no form (host logic only).  `tile_bytes`: what
+    et_epipolar_backward_tiled_workspace_bytes answers for the shape, 0 where the tile path does not apply."""
+    if not use_workspace:
+        return "atomic"
+    form = "tile" if tile_bytes > 0 and not (spec.variant & _BWD_EXPLICIT) else "gather"
+    if spec.variant & _lib.ET_VARIANT_BWD_DETERMINISTIC:
+        # prefer the deterministic tile form; where it does not apply "gather" is the (bit-reproducible) choice
+        form = "tile_det" if form == "tile" and spec.softmax_enabled else "gather"
+    return form
+
+
 def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, form=None, attn=None, workspace=None):
     """d(feat_ref), d(feat_src) of forward_nhwc.  Four forms of the same gradient:
       "tile"    MFMA tile formulation, d(feat_src) accumulated with float atomics across tiles: fastest,
@@ -542,11 +571,16 @@ def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, 
       "gather"  per-(pixel,row) coefficients -> counting sort -> ordered per-row sums: no float atomics, bit-reproducible;
       "atomic"  bilinear-transpose scatter with float atomics (no workspace).
     form=None picks "tile" where it applies (unless the spec's variant names a backward form or NO_TILE) -- "tile_det" when the
-    variant carries ET_VARIANT_BWD_DETERMINISTIC and the soft-max is on --, else "gather"; use_workspace=False means "atomic".  `attn`: the attention forward_nhwc returned for the same inputs
+    variant carries ET_VARIANT_BWD_DETERMINISTIC and the soft-max is on --, else "gather"; use_workspace=False means "atomic"
+    (_default_backward_form).  `attn`: the attention forward_nhwc returned for the same inputs
     (N,K,H,W) -- the tile form then does not recompute the soft-max (one GEMM of five less); the other forms ignore it.
     `workspace`: a caller-owned uint8 tensor for the "tile" / "gather" form instead of the cached one (the tile form's has
     the forward's layout and size: tile_workspace)."""
-    n, h, w, c = ref.shape
+    n, h, w, c = _require_pair(spec, ref, src, cam)
+    _require_gpu(grad_out, "grad_out")
+    if grad_out.shape != ref.shape or grad_out.device != ref.device:
+        raise ValueError("grad_out must be a float32 %s tensor on %s, got %s on %s" %
+                         (tuple(ref.shape), ref.device, tuple(grad_out.shape), grad_out.device))
     xs, ys, steps = spec.constants(ref.device)
     grad_out = grad_out.contiguous()
     g_ref = _empty(None, like=ref)
@@ -555,46 +589,31 @@ def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, 
     lib = _lib.load()
     tile_bytes = int(lib.et_epipolar_backward_tiled_workspace_bytes(ctypes.byref(d)))
     if form is None:
-        if not use_workspace:
-            form = "atomic"
-        else:
-            form = "tile" if tile_bytes > 0 and not (d.variant & _BWD_EXPLICIT) else "gather"
-            if spec.variant & _lib.ET_VARIANT_BWD_DETERMINISTIC:
-                # prefer the deterministic tile form; where it does not apply "gather" is the (bit-reproducible) choice
-                form = "tile_det" if form == "tile" and spec.softmax_enabled else "gather"
+        form = _default_backward_form(spec, tile_bytes, use_workspace)
     if form not in ("tile", "tile_det", "gather", "atomic"):
         raise ValueError("unknown backward form %r" % (form,))
     args = (ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(ref), _ptr(src), _ptr(grad_out),
             _ptr(g_ref), _ptr(g_src))
-    with torch.cuda.device(ref.device):
-        if form == "tile":
-            if tile_bytes == 0:
-                raise _lib.EpipolarAmdError("the tiled backward needs the 256-channel head (got C=%d, K=%d, %dx%d)" % (c, spec.K, h, w))
-            ws = _own_workspace(workspace, tile_bytes, ref.device, "fwd")
-            _last_tile_backward_ws[(ref.device.index, torch.cuda.current_stream(ref.device).cuda_stream)] = weakref.ref(ws)
-            if attn is not None:
-                assert attn.is_cuda and attn.dtype == torch.float32 and tuple(attn.shape) == (n, spec.K, h, w) and attn.is_contiguous()
-            _lib.check(lib.et_epipolar_backward_tiled_attn(*args[:7], _ptr(attn), *args[7:], _ptr(ws), ctypes.c_size_t(tile_bytes),
-                                                           _stream(ref)), "et_epipolar_backward_tiled_attn")
-        elif form == "tile_det":
-            det_bytes = int(lib.et_epipolar_backward_tiled_det_workspace_bytes(ctypes.byref(d)))
-            if det_bytes == 0:
-                raise _lib.EpipolarAmdError("the tiled backward needs the 256-channel head (got C=%d, K=%d, %dx%d)" % (c, spec.K, h, w))
-            ws = _own_workspace(workspace, det_bytes, ref.device, "fwd")
-            _last_tile_backward_ws[(ref.device.index, torch.cuda.current_stream(ref.device).cuda_stream)] = weakref.ref(ws)
-            if attn is not None:
-                assert attn.is_cuda and attn.dtype == torch.float32 and tuple(attn.shape) == (n, spec.K, h, w) and attn.is_contiguous()
-            _lib.check(lib.et_epipolar_backward_tiled_det(*args[:7], _ptr(attn), *args[7:], _ptr(ws), ctypes.c_size_t(ws.numel()),
-                                                          _stream(ref)), "et_epipolar_backward_tiled_det")
-            if POISON_OUTPUTS:          # (test suite: the guard bit surfaces at the call that set it)
-                check_tile_errors(workspace=ws)
-        else:
-            ws, ws_bytes = None, 0
-            if form == "gather":
-                ws_bytes = int(lib.et_epipolar_backward_workspace_bytes(ctypes.byref(d)))
-                ws = _own_workspace(workspace, ws_bytes, ref.device, "bwd")
-            _lib.check(lib.et_epipolar_backward(*args, _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(ref)),
-                       "et_epipolar_backward")
+    if form in ("tile", "tile_det"):
+        det = form == "tile_det"
+        need = int(lib.et_epipolar_backward_tiled_det_workspace_bytes(ctypes.byref(d))) if det else tile_bytes
+        if need == 0:
+            raise _lib.EpipolarAmdError("the tiled backward needs the 256-channel head (got C=%d, K=%d, %dx%d)" % (c, spec.K, h, w))
+        ws = _own_workspace(workspace, need, ref.device, "fwd")
+        _last_tile_backward_ws[(ref.device.index, torch.cuda.current_stream(ref.device).cuda_stream)] = weakref.ref(ws)
+        if attn is not None:
+            _require_f32(attn, "attn", ref.device, (n, spec.K, h, w))
+        # (the attention form of the float tile backward is handed the bytes it asked for, the deterministic form all it may use)
+        _call("et_epipolar_backward_tiled_det" if det else "et_epipolar_backward_tiled_attn", ref, *args[:7], _ptr(attn), *args[7:],
+              _ptr(ws), ctypes.c_size_t(ws.numel() if det else tile_bytes), _stream(ref))
+        if det and POISON_OUTPUTS:          # (test suite: the guard bit surfaces at the call that set it)
+            check_tile_errors(workspace=ws)
+    else:
+        ws, ws_bytes = None, 0
+        if form == "gather":
+            ws_bytes = int(lib.et_epipolar_backward_workspace_bytes(ctypes.byref(d)))
+            ws = _own_workspace(workspace, ws_bytes, ref.device, "bwd")
+        _call("et_epipolar_backward", ref, *args, _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(ref))
     return g_ref, g_src
 
 
@@ -615,10 +634,9 @@ def backward_deferred_tiles(device, header=False, workspace=None):
         ref = _last_tile_backward_ws.get((idx, torch.cuda.current_stream(dev).cuda_stream))
         buf = ref() if ref is not None else None
     if buf is None:
-        return (0,) * 8 if header else 0
-    base = (-buf.data_ptr()) % 256
-    words = buf[base:base + 32].view(torch.int32).tolist()       # (eight header words)
-    return tuple(words) if header else words[0]
+        return (0,) * _HEADER_DIAGNOSTICS if header else 0
+    words = _header(buf)[:_HEADER_DIAGNOSTICS].tolist()
+    return tuple(words) if header else words[_HEADER_DEFERRED]
 
 
 def atomic_probe(device, rows: int = 1 << 18, blocks: int = 2048, iters: int = 256, reps: int = 5) -> dict:
@@ -627,13 +645,12 @@ def atomic_probe(device, rows: int = 1 << 18, blocks: int = 2048, iters: int = 2
     a (rows, 256) fp32 array, 1 GB by default, nothing else in the kernel).  A diagnostic for bench.py: synchronises."""
     dev = torch.device(device)
     dst = torch.zeros(rows, 256, device=dev)
-    lib = _lib.load()
     ms = []
     with torch.cuda.device(dev):
         for r in range(reps + 1):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
-            _lib.check(lib.et_debug_atomic_probe(_ptr(dst), rows, blocks, iters, _stream(dst)), "et_debug_atomic_probe")
+            _call("et_debug_atomic_probe", None, _ptr(dst), rows, blocks, iters, _stream(dst))
             b.record()
             torch.cuda.synchronize(dev)
             if r:
@@ -646,13 +663,15 @@ def atomic_probe(device, rows: int = 1 << 18, blocks: int = 2048, iters: int = 2
 
 def residual_epilogue(feat, out, y=None, scale=None, shift=None, want_finalout=True, want_x=True):
     """All (N,H,W,C) contiguous.  finalout = out + y*scale + shift ; x = feat + finalout."""
+    _require_f32(out, "out", out.device)
     n, h, w, c = out.shape
+    for t, nm, size in ((feat, "feat", out.numel()), (y, "y", out.numel()), (scale, "scale", c), (shift, "shift", c)):
+        if t is not None:       # (feat / y: out's rows in any shape)
+            _require_vector(t, nm, size, out.device)
     fin = _empty(None, like=out) if want_finalout else None
     x = _empty(None, like=out) if want_x else None
-    with torch.cuda.device(out.device):
-        _lib.check(_lib.load().et_residual_epilogue(n * h * w, c, _ptr(feat), _ptr(out), _ptr(y), _ptr(scale),
-                                                    _ptr(shift), _ptr(fin), _ptr(x), _stream(out)),
-                   "et_residual_epilogue")
+    _call("et_residual_epilogue", out, n * h * w, c, _ptr(feat), _ptr(out), _ptr(y), _ptr(scale), _ptr(shift), _ptr(fin), _ptr(x),
+          _stream(out))
     return fin, x
 
 
@@ -660,26 +679,30 @@ def residual_gemm_pack(wf: torch.Tensor) -> torch.Tensor:
     """Lay the folded (256 out, 256 in) fp32 weight of the z branch out for `residual_gemm` (split fp16 MFMA fragments +
     the scale).  Returns the packed uint8 buffer; repack when the weights change."""
     _require_gpu(wf, "wf")
-    assert wf.dtype == torch.float32 and tuple(wf.shape) == (256, 256), "residual_gemm is written for the 256-channel head"
+    if tuple(wf.shape) != (256, 256):
+        raise ValueError("residual_gemm is written for the 256-channel head")
     wf = wf.contiguous()
-    lib = _lib.load()
-    packed = torch.empty(int(lib.et_residual_gemm_packed_bytes()), dtype=torch.uint8, device=wf.device)
-    with torch.cuda.device(wf.device):
-        _lib.check(lib.et_residual_gemm_pack(_ptr(wf), _ptr(packed), _stream(wf)), "et_residual_gemm_pack")
+    packed = torch.empty(int(_lib.load().et_residual_gemm_packed_bytes()), dtype=torch.uint8, device=wf.device)
+    _call("et_residual_gemm_pack", wf, _ptr(wf), _ptr(packed), _stream(wf))
     return packed
+
+
+def _require_packed(packed: torch.Tensor, name: str, device):
+    _require_bytes(packed, name, int(_lib.load().et_residual_gemm_packed_bytes()), device,
+                   "%s must be the buffer residual_gemm_pack returns" % name)
 
 
 def residual_gemm(out: torch.Tensor, packed: torch.Tensor, bias: torch.Tensor, feat: torch.Tensor = None) -> torch.Tensor:
     """x = [feat +] bias + out @ Wf^T over the last dimension (256), everything (..., 256) fp32 contiguous: the
     eval-mode `bn(z(out)) [+ out] [+ feat]` (epipolar.py:250-253, resnet.py:388) as one HBM-bound kernel."""
-    _require_gpu(out, "out")
+    _require_f32(out, "out", out.device)
     c = out.shape[-1]
-    assert out.is_contiguous() and (feat is None or (feat.is_contiguous() and feat.shape == out.shape))
-    assert bias.is_cuda and bias.numel() == c and bias.is_contiguous()
+    if feat is not None:
+        _require_f32(feat, "feat", out.device, out.shape)
+    _require_vector(bias, "bias", c, out.device)
+    _require_packed(packed, "packed", out.device)
     x = _empty(None, like=out)
-    with torch.cuda.device(out.device):
-        _lib.check(_lib.load().et_residual_gemm(out.numel() // c, c, _ptr(out), _ptr(feat), _ptr(packed), _ptr(bias), _ptr(x),
-                                                _stream(out)), "et_residual_gemm")
+    _call("et_residual_gemm", out, out.numel() // c, c, _ptr(out), _ptr(feat), _ptr(packed), _ptr(bias), _ptr(x), _stream(out))
     return x
 
 
@@ -687,24 +710,18 @@ def z_batch_stats(out: torch.Tensor, packed_wz: torch.Tensor, z_bias: torch.Tens
     """First pass of the training-mode epilogue (et_z_batch_stats): y = out @ Wz^T + z_bias over the last dimension (256)
     and its per-channel batch mean / biased variance over all rows.  Returns (y, mean, var).  `workspace`: a caller-owned uint8
     tensor instead of the cached one (any contents)."""
-    _require_gpu(out, "out")
+    _require_f32(out, "out", out.device, (..., 256), "out must be a contiguous (..., 256) tensor")
     c = out.shape[-1]
-    if c != 256 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous (..., 256) tensor")
-    if not (z_bias.is_cuda and z_bias.numel() == c and z_bias.is_contiguous() and z_bias.dtype == torch.float32):
-        raise ValueError("z_bias must be a contiguous float32 vector of 256 values on the GPU")
-    lib = _lib.load()
-    if packed_wz.numel() < int(lib.et_residual_gemm_packed_bytes()) or packed_wz.dtype != torch.uint8 or not packed_wz.is_cuda:
-        raise ValueError("packed_wz must be the buffer residual_gemm_pack returns")
+    _require_vector(z_bias, "z_bias", c, out.device)
+    _require_packed(packed_wz, "packed_wz", out.device)
     rows = out.numel() // c
     y = _empty(None, like=out)
     mean = _empty((c,), device=out.device)
     var = _empty((c,), device=out.device)
-    with torch.cuda.device(out.device):
-        ws_bytes = int(lib.et_z_batch_stats_workspace_bytes(rows))
-        ws = _own_workspace(workspace, ws_bytes, out.device, "zstats")
-        _lib.check(lib.et_z_batch_stats(rows, c, _ptr(out), _ptr(packed_wz), _ptr(z_bias), _ptr(y), _ptr(mean), _ptr(var), _ptr(ws),
-                                        ctypes.c_size_t(ws_bytes), _stream(out)), "et_z_batch_stats")
+    ws_bytes = int(_lib.load().et_z_batch_stats_workspace_bytes(rows))
+    ws = _own_workspace(workspace, ws_bytes, out.device, "zstats")
+    _call("et_z_batch_stats", out, rows, c, _ptr(out), _ptr(packed_wz), _ptr(z_bias), _ptr(y), _ptr(mean), _ptr(var), _ptr(ws),
+          ctypes.c_size_t(ws_bytes), _stream(out))
     return y, mean, var
 
 
@@ -713,26 +730,19 @@ def z_backward(g: torch.Tensor, y: torch.Tensor, mean: torch.Tensor, invstd: tor
     """Backward of the training-mode epilogue w.r.t. `out` and the batch norm's affine parameters (et_z_backward): g, y
     (..., 256) contiguous.  Returns (grad_out, grad_y, grad_gamma, grad_beta).  `workspace`: a caller-owned uint8 tensor instead
     of the cached one (any contents)."""
-    _require_gpu(g, "g")
-    _require_gpu(y, "y")
+    _require_f32(g, "g", g.device, (..., 256), "g and y must be contiguous (..., 256) tensors of one shape")
+    _require_f32(y, "y", g.device, g.shape, "g and y must be contiguous (..., 256) tensors of one shape")
     c = g.shape[-1]
-    if c != 256 or g.shape != y.shape or not (g.is_contiguous() and y.is_contiguous()):
-        raise ValueError("g and y must be contiguous (..., 256) tensors of one shape")
     for t, nm in ((mean, "mean"), (invstd, "invstd"), (gamma, "gamma")):
-        if not (t.is_cuda and t.numel() == c and t.is_contiguous() and t.dtype == torch.float32):
-            raise ValueError("%s must be a contiguous float32 vector of 256 values on the GPU" % nm)
-    lib = _lib.load()
-    if packed_wzt.numel() < int(lib.et_residual_gemm_packed_bytes()) or packed_wzt.dtype != torch.uint8 or not packed_wzt.is_cuda:
-        raise ValueError("packed_wzt must be the buffer residual_gemm_pack returns")
+        _require_vector(t, nm, c, g.device)
+    _require_packed(packed_wzt, "packed_wzt", g.device)
     rows = g.numel() // c
     gout, gy = _empty(None, like=g), _empty(None, like=g)
     ggamma, gbeta = _empty((c,), device=g.device), _empty((c,), device=g.device)
-    with torch.cuda.device(g.device):
-        ws_bytes = int(lib.et_z_backward_workspace_bytes(rows))
-        ws = _own_workspace(workspace, ws_bytes, g.device, "zbwd")
-        _lib.check(lib.et_z_backward(rows, c, _ptr(g), _ptr(y), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(packed_wzt),
-                                     1 if zresidual else 0, _ptr(gout), _ptr(gy), _ptr(ggamma), _ptr(gbeta), _ptr(ws),
-                                     ctypes.c_size_t(ws_bytes), _stream(g)), "et_z_backward")
+    ws_bytes = int(_lib.load().et_z_backward_workspace_bytes(rows))
+    ws = _own_workspace(workspace, ws_bytes, g.device, "zbwd")
+    _call("et_z_backward", g, rows, c, _ptr(g), _ptr(y), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(packed_wzt),
+          1 if zresidual else 0, _ptr(gout), _ptr(gy), _ptr(ggamma), _ptr(gbeta), _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(g))
     return gout, gy, ggamma, gbeta
 
 
@@ -740,19 +750,16 @@ def z_wgrad(grad_y: torch.Tensor, out: torch.Tensor, workspace: torch.Tensor = N
     """d Wz (256, 256) = grad_y^T @ out and d bz (256) = grad_y.sum(rows) over (..., 256) contiguous tensors (et_z_wgrad:
     three-term bf16 MFMAs with fp32 accumulation, no atomics, bit-reproducible).  `workspace`: a caller-owned uint8 tensor
     instead of the cached one (any contents)."""
-    _require_gpu(grad_y, "grad_y")
-    _require_gpu(out, "out")
+    _require_f32(grad_y, "grad_y", grad_y.device, (..., 256), "grad_y and out must be contiguous (..., 256) tensors of one shape")
+    _require_f32(out, "out", grad_y.device, grad_y.shape, "grad_y and out must be contiguous (..., 256) tensors of one shape")
     c = out.shape[-1]
-    if c != 256 or grad_y.shape != out.shape or not (grad_y.is_contiguous() and out.is_contiguous()):
-        raise ValueError("grad_y and out must be contiguous (..., 256) tensors of one shape")
     rows = out.numel() // c
     gw, gb = _empty((c, c), device=out.device), _empty((c,), device=out.device)
-    lib = _lib.load()
     with torch.cuda.device(out.device):
-        ws_bytes = int(lib.et_z_wgrad_workspace_bytes(rows))     # (sized by the CU count of the CURRENT device: inside the guard)
+        ws_bytes = int(_lib.load().et_z_wgrad_workspace_bytes(rows))     # (sized by the CU count of the CURRENT device: inside the guard)
         ws = _own_workspace(workspace, ws_bytes, out.device, "zwgrad")
-        _lib.check(lib.et_z_wgrad(rows, c, _ptr(grad_y), _ptr(out), _ptr(gw), _ptr(gb), _ptr(ws), ctypes.c_size_t(ws_bytes),
-                                  _stream(out)), "et_z_wgrad")
+        _call("et_z_wgrad", None, rows, c, _ptr(grad_y), _ptr(out), _ptr(gw), _ptr(gb), _ptr(ws), ctypes.c_size_t(ws_bytes),
+              _stream(out))
     return gw, gb
 
 
@@ -765,10 +772,8 @@ def heatmap_peaks(heatmaps: torch.Tensor, radius: float, downsample: float, thre
     hm = heatmaps.detach().contiguous()
     locs = _empty((n, j, 2), device=hm.device)
     scores = _empty((n, j), device=hm.device)
-    with torch.cuda.device(hm.device):
-        _lib.check(_lib.load().et_heatmap_peaks(n * j, h, w, _ptr(hm), float(radius), float(downsample), float(threshold),
-                                                int(bool(legacy_floor_division)), _ptr(locs), _ptr(scores), _stream(hm)),
-                   "et_heatmap_peaks")
+    _call("et_heatmap_peaks", hm, n * j, h, w, _ptr(hm), float(radius), float(downsample), float(threshold),
+          int(bool(legacy_floor_division)), _ptr(locs), _ptr(scores), _stream(hm))
     return locs, scores
 
 
