@@ -70,6 +70,7 @@ _SIGNATURES = {
     "et_epipolar_forward": (ctypes.c_int, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "et_epipolar_forward_general": (ctypes.c_int, [_D] + [_P] * 8 + [ctypes.c_int32] * 3 + [_P] * 4),
     "et_epipolar_backward_general": (ctypes.c_int, [_D] + [_P] * 9 + [ctypes.c_int32] * 3 + [_P] * 5),
+    "et_epipolar_backward_general_ga": (ctypes.c_int, [_D] + [_P] * 10 + [ctypes.c_int32] * 3 + [_P] * 5),
     "et_epipolar_forward_workspace_bytes": (ctypes.c_size_t, [_D]),
     "et_epipolar_forward_workspace_stats_offset": (ctypes.c_size_t, [_D]),
     "et_epipolar_forward_workspace_error_offset": (ctypes.c_size_t, [_D]),
@@ -78,11 +79,15 @@ _SIGNATURES = {
     "et_epipolar_backward_tiled_workspace_bytes": (ctypes.c_size_t, [_D]),
     "et_epipolar_backward_tiled": (ctypes.c_int, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "et_epipolar_backward_tiled_attn": (ctypes.c_int, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "et_epipolar_backward_tiled_ga": (ctypes.c_int, [_D] + [_P] * 12 + [ctypes.c_size_t, _P]),
     "et_epipolar_backward_tiled_det_workspace_bytes": (ctypes.c_size_t, [_D]),
     "et_epipolar_backward_tiled_det": (ctypes.c_int, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "et_debug_host_det_quantum": (ctypes.c_int, [_D, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, _P]),
+    "et_epipolar_backward_tiled_det_ga": (ctypes.c_int, [_D] + [_P] * 12 + [ctypes.c_size_t, _P]),
+    "et_debug_host_det_quantum_ga": (ctypes.c_int, [_D] + [ctypes.c_float] * 4 + [_P, _P]),
     "et_epipolar_backward_workspace_bytes": (ctypes.c_size_t, [_D]),
     "et_epipolar_backward": (ctypes.c_int, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "et_epipolar_backward_ga": (ctypes.c_int, [_D] + [_P] * 11 + [ctypes.c_size_t, _P]),
     "et_residual_epilogue": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "et_residual_gemm_packed_bytes": (ctypes.c_size_t, []),
     "et_residual_gemm_pack": (ctypes.c_int, [_P, _P, _P]),

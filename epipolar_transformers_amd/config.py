@@ -184,6 +184,8 @@ def default_cfg() -> CfgNode:
     C.EPIPOLAR_AMD.VARIANT = 0                # EtLayerDesc.variant bits
     C.EPIPOLAR_AMD.DETERMINISTIC = False      # bit-reproducible training: the layer's backward takes the integer-sum tile form
                                               # (ET_VARIANT_BWD_DETERMINISTIC); option branches raise on backward instead
+    C.EPIPOLAR_AMD.ATTN_GRAD = False          # True: the `depth` (attention) Epipolar.forward returns carries gradient, as in the
+                                              # reference (epipolar.py:245, 263) -- a loss on it trains the features (HIP kernels)
     C.EPIPOLAR_AMD.FUSED_EPILOGUE = True      # eval: fold BN and fuse the residual adds in one kernel
     C.EPIPOLAR_AMD.SHARD_P2P = False          # view-sharded partition: source maps by one all-to-all (each block to the rank that
                                               # samples it) instead of the all-gather BASELINE.json's north star names (G x the bytes)

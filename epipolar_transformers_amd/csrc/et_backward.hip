@@ -1,4 +1,4 @@
-// libepipolar_amd.so: the backward for any shape (et_epipolar_backward).
+// libepipolar_amd.so: the backward for any shape (et_epipolar_backward, et_epipolar_backward_ga).
 #include "et_common.h"
 
 namespace {
@@ -30,6 +30,15 @@ int et_epipolar_backward(const EtLayerDesc *desc, const float *xs, const float *
                          const float *grad_out, float *grad_ref, float *grad_src, void *workspace,
                          size_t workspace_bytes, void *stream)
 {
+    return et_epipolar_backward_ga(desc, xs, ys, steps, cam, feat_ref, feat_src, grad_out, nullptr, grad_ref, grad_src, workspace,
+                                   workspace_bytes, stream);
+}
+
+int et_epipolar_backward_ga(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                            const float *cam, const float *feat_ref, const float *feat_src,
+                            const float *grad_out, const float *grad_attn, float *grad_ref, float *grad_src, void *workspace,
+                            size_t workspace_bytes, void *stream)
+{
     if (int e = validate(desc)) return e;
     if (!xs || !ys || !steps || !cam || !feat_ref || !feat_src || !grad_out || !grad_ref || !grad_src)
         return fail("et_epipolar_backward: NULL pointer");
@@ -47,7 +56,7 @@ int et_epipolar_backward(const EtLayerDesc *desc, const float *xs, const float *
     std::memset(&p, 0, sizeof(p));
     p.d = *desc;
     p.xs = xs; p.ys = ys; p.steps = steps; p.cam = cam;
-    p.fref = feat_ref; p.fsrc = feat_src; p.gout = grad_out;
+    p.fref = feat_ref; p.fsrc = feat_src; p.gout = grad_out; p.gattn = grad_attn;
     p.gref = grad_ref; p.gsrc = grad_src;
     p.blocks_per_pair = (HW + kPixPerBlock - 1) / kPixPerBlock;
     const long long total = (long long)p.blocks_per_pair * desc->N;

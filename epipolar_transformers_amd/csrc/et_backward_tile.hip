@@ -1,4 +1,4 @@
-// libepipolar_amd.so: the MFMA tile formulation of the backward (et_epipolar_backward_tiled, _attn, _det).
+// libepipolar_amd.so: the MFMA tile formulation of the backward (et_epipolar_backward_tiled, _attn, _det and their _ga forms).
 // Kernels: the ordering (kernels_tile_order.inc, through et_tile_host.h) and the tile kernel (kernels_backward_tile.inc over
 // kernels_tile_common.inc, the helpers shared with the forward).
 #include <algorithm>
@@ -32,7 +32,7 @@ DetWorkspace carve_det_workspace(const TileWorkspace &w, size_t tiles, size_t pa
 }
 int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
                         const float *cam, const float *feat_ref, const float *feat_src, const float *attn,
-                        const float *grad_out, float *grad_ref, float *grad_src, void *workspace,
+                        const float *grad_out, const float *grad_attn, float *grad_ref, float *grad_src, void *workspace,
                         size_t workspace_bytes, void *stream);
 }  // namespace
 
@@ -45,24 +45,39 @@ size_t et_epipolar_backward_tiled_det_workspace_bytes(const EtLayerDesc *desc)
     return fwd + det_extra_bytes((size_t)desc->N, (size_t)desc->H * desc->W);
 }
 
+int et_epipolar_backward_tiled_det_ga(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                                      const float *cam, const float *feat_ref, const float *feat_src, const float *attn,
+                                      const float *grad_out, const float *grad_attn, float *grad_ref, float *grad_src,
+                                      void *workspace, size_t workspace_bytes, void *stream)
+{
+    return backward_tiled_impl(true, desc, xs, ys, steps, cam, feat_ref, feat_src, attn, grad_out, grad_attn, grad_ref, grad_src,
+                               workspace, workspace_bytes, stream);
+}
+
 int et_epipolar_backward_tiled_det(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
                                    const float *cam, const float *feat_ref, const float *feat_src, const float *attn,
                                    const float *grad_out, float *grad_ref, float *grad_src, void *workspace,
                                    size_t workspace_bytes, void *stream)
 {
-    return backward_tiled_impl(true, desc, xs, ys, steps, cam, feat_ref, feat_src, attn, grad_out, grad_ref, grad_src, workspace,
-                               workspace_bytes, stream);
+    return et_epipolar_backward_tiled_det_ga(desc, xs, ys, steps, cam, feat_ref, feat_src, attn, grad_out, nullptr, grad_ref, grad_src,
+                                             workspace, workspace_bytes, stream);
+}
+
+int et_debug_host_det_quantum_ga(const EtLayerDesc *desc, float m_ref, float m_src, float m_g, float m_ga, float *q, float *bound)
+{
+    if (!desc || !q || !bound) return fail("et_debug_host_det_quantum: NULL pointer");
+    if (!desc->softmax_enabled) return fail("et_debug_host_det_quantum: no bound with the soft-max off (sim / K is unbounded)");
+    if (!(m_ref >= 0.f) || !(m_src >= 0.f) || !(m_g >= 0.f) || !(m_ga >= 0.f))
+        return fail("et_debug_host_det_quantum: maxima must be >= 0");
+    const DetQuantum r = det_quantum(desc->softmax_scale, m_ref, m_src, m_g, m_ga);
+    *q = r.q;
+    *bound = r.bound;
+    return 0;
 }
 
 int et_debug_host_det_quantum(const EtLayerDesc *desc, float m_ref, float m_src, float m_g, float *q, float *bound)
 {
-    if (!desc || !q || !bound) return fail("et_debug_host_det_quantum: NULL pointer");
-    if (!desc->softmax_enabled) return fail("et_debug_host_det_quantum: no bound with the soft-max off (sim / K is unbounded)");
-    if (!(m_ref >= 0.f) || !(m_src >= 0.f) || !(m_g >= 0.f)) return fail("et_debug_host_det_quantum: maxima must be >= 0");
-    const DetQuantum r = det_quantum(desc->softmax_scale, m_ref, m_src, m_g);
-    *q = r.q;
-    *bound = r.bound;
-    return 0;
+    return et_debug_host_det_quantum_ga(desc, m_ref, m_src, m_g, 0.f, q, bound);
 }
 
 size_t et_epipolar_backward_tiled_workspace_bytes(const EtLayerDesc *desc)
@@ -71,13 +86,22 @@ size_t et_epipolar_backward_tiled_workspace_bytes(const EtLayerDesc *desc)
     return et_epipolar_forward_workspace_bytes(desc);
 }
 
+int et_epipolar_backward_tiled_ga(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                                  const float *cam, const float *feat_ref, const float *feat_src, const float *attn,
+                                  const float *grad_out, const float *grad_attn, float *grad_ref, float *grad_src,
+                                  void *workspace, size_t workspace_bytes, void *stream)
+{
+    return backward_tiled_impl(false, desc, xs, ys, steps, cam, feat_ref, feat_src, attn, grad_out, grad_attn, grad_ref, grad_src,
+                               workspace, workspace_bytes, stream);
+}
+
 int et_epipolar_backward_tiled(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
                                const float *cam, const float *feat_ref, const float *feat_src,
                                const float *grad_out, float *grad_ref, float *grad_src, void *workspace,
                                size_t workspace_bytes, void *stream)
 {
-    return backward_tiled_impl(false, desc, xs, ys, steps, cam, feat_ref, feat_src, nullptr, grad_out, grad_ref, grad_src,
-                               workspace, workspace_bytes, stream);
+    return et_epipolar_backward_tiled_ga(desc, xs, ys, steps, cam, feat_ref, feat_src, nullptr, grad_out, nullptr, grad_ref, grad_src,
+                                         workspace, workspace_bytes, stream);
 }
 
 int et_epipolar_backward_tiled_attn(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
@@ -85,8 +109,8 @@ int et_epipolar_backward_tiled_attn(const EtLayerDesc *desc, const float *xs, co
                                     const float *grad_out, float *grad_ref, float *grad_src, void *workspace,
                                     size_t workspace_bytes, void *stream)
 {
-    return backward_tiled_impl(false, desc, xs, ys, steps, cam, feat_ref, feat_src, attn, grad_out, grad_ref, grad_src, workspace,
-                               workspace_bytes, stream);
+    return et_epipolar_backward_tiled_ga(desc, xs, ys, steps, cam, feat_ref, feat_src, attn, grad_out, nullptr, grad_ref, grad_src,
+                                         workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"
@@ -131,7 +155,7 @@ int launch_bwd_tile_list_as(const BwdTileParams &tp, bool det, int dev, hipStrea
 
 int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
                         const float *cam, const float *feat_ref, const float *feat_src, const float *attn,
-                        const float *grad_out, float *grad_ref, float *grad_src, void *workspace,
+                        const float *grad_out, const float *grad_attn, float *grad_ref, float *grad_src, void *workspace,
                         size_t workspace_bytes, void *stream)
 {
     const char *bad_args = (!xs || !ys || !steps || !cam || !feat_ref || !feat_src || !grad_out || !grad_ref || !grad_src) ? "NULL pointer" : nullptr;
@@ -151,7 +175,7 @@ int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, cons
     BwdParams &p = tp.b;
     p.d = *desc;
     p.xs = xs; p.ys = ys; p.steps = steps; p.cam = cam;
-    p.fref = feat_ref; p.fsrc = feat_src; p.gout = grad_out;
+    p.fref = feat_ref; p.fsrc = feat_src; p.gout = grad_out; p.gattn = grad_attn;
     p.gref = grad_ref; p.gsrc = grad_src;
     p.blocks_per_pair = c.tiles_per_pair;
     p.total_blocks = c.total;
@@ -178,7 +202,7 @@ int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, cons
         // the pair's exact maxima -> its quantum (kernels_backward_det.inc)
         hipLaunchKernelGGL(det_maxima_kernel, dim3(kDetMaxBlocks, desc->N), dim3(256), 0, st, reinterpret_cast<const float4 *>(feat_ref),
                            reinterpret_cast<const float4 *>(feat_src), reinterpret_cast<const float4 *>(grad_out), vec4_per_pair,
-                           dw.partial);
+                           grad_attn, (unsigned)desc->K * (unsigned)HW, dw.partial);
         hipLaunchKernelGGL(det_quantum_kernel, dim3((desc->N + 63) / 64), dim3(64), 0, st, desc->N, kDetMaxBlocks, desc->softmax_scale,
                            dw.partial, dw.quanta);
         if (int e = check_launch("et_epipolar_backward_tiled_det(quantum)")) return e;

@@ -90,6 +90,7 @@ struct BwdParams {
     EtLayerDesc d;
     const float *xs, *ys, *steps, *cam;
     const float *fref, *fsrc, *gout;
+    const float *gattn;  // nullable: d loss / d attn (N,K,H,W), added to e_k = g . S_k in front of the soft-max gradient
     float *gref, *gsrc;
     int blocks_per_pair;
     int total_blocks;

@@ -251,12 +251,16 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_fwd_general_kernel(
 //      d V_k' = a_k' g
 //  ATTENTION max (:222-235, 282-286): out = V of the first arg-max of the raw cosine -- a one-hot a, no gradient through the
 //  similarity.  SIMILARITY prior (:288-289): a = the prior table itself: d prior_k' = d a_k', nothing through q / P.
+//  A gradient through the returned attention, ga = d loss / d attn (nullable), joins d a: every line above holds with
+//  d a_k' = g . V_k' + ga_k'.  ATTENTION max returns the raw cosine as its attention: d s_k' = ga_k' (no mask), through the cosine
+//  derivative above; with SIMILARITY prior beside it the returned weights are the table: d prior_k' = ga_k'.
 //  d P / d V go through the per-channel maximum to the sample that won (the first on a tie, as torch.max), times the four
 //  bilinear weights onto the taps of the maps: float atomics (the sums over pixels arrive in any order: reproducible to
 //  rounding only, like the tile backward).  The similarities are recomputed (nothing but the inputs is saved by the forward).
 struct GeneralBwdParams {
     GeneralParams f;        // inputs as in the forward (out / attn / corr unused)
     const float *gout;      // (N, H*W, cv)
+    const float *gattn;     // (N, K', H*W)  nullable: d loss / d attn, joins d a_k' = g . V_k'
     float *gq;              // (N, H*W, cs)  written
     float *gsim;            // (N, H*W, cs)  nullable, accumulated with atomics: zero it first
     float *gval;            // (N, H*W, cv)  nullable, accumulated with atomics: zero it first
@@ -373,12 +377,23 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_bwd_general_kernel(
             np_[s] = p.cosine ? fmaxf(sqrtf(in ? s_b[k] : 1.f), kEps) : 1.f;
             sim[s] = p.cosine ? raw / (nq * np_[s]) : raw;           // (the forward's expression)
             da[s] = in ? s_a[k] : 0.f;
+            if (bp.gattn && in) da[s] += bp.gattn[((size_t)n * Ks + k) * HW + pix];     // (block-uniform pointer test)
             pr[s] = (in && p.prior) ? p.prior[((size_t)n * Ks + k) * HW + pix] : 0.f;
             if (p.sim_prior) sim[s] = pr[s];
             aout[s] = alpha[s] = beta[s] = dprior[s] = 0.f;
         }
+        // d s_k' -> the coefficients of the maps' gradients (dot: alpha; cosine: alpha, beta, gamma)
+        auto through_similarity = [&](int s, float ds) {
+            if (p.cosine) {
+                alpha[s] = ds / (nq * np_[s]);
+                beta[s] = (np_[s] > kEps) ? ds * sim[s] / (np_[s] * np_[s]) : 0.f;
+                gamma += (nq > kEps) ? ds * sim[s] / (nq * nq) : 0.f;
+            } else {
+                alpha[s] = ds;
+            }
+        };
         if (p.attn_max) {
-            // first maximum over k' (torch.argmax): a one-hot weight, nothing flows through the similarity
+            // first maximum over k' (torch.argmax): a one-hot weight, nothing flows from `out` through the similarity
             float bestv = neg_inf, bestk = 1e9f;
 #pragma unroll
             for (int s = 0; s < KPL; ++s) {
@@ -392,6 +407,15 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_bwd_general_kernel(
             const int besti = (int)wave_all_min((bestv == bm) ? bestk : 1e9f);
 #pragma unroll
             for (int s = 0; s < KPL; ++s) aout[s] = (s * kWave + lane == besti) ? 1.f : 0.f;
+            if (bp.gattn) {
+                // ... but the returned attention is the raw cosine (or the given weights) itself: d s_k' = ga_k' (da holds it:
+                // no g . V_k' in this mode), no mask
+#pragma unroll
+                for (int s = 0; s < KPL; ++s) {
+                    if (p.sim_prior) dprior[s] = da[s];
+                    else through_similarity(s, (s * kWave + lane < Ks) ? da[s] : 0.f);
+                }
+            }
         } else if (p.sim_prior) {
 #pragma unroll
             for (int s = 0; s < KPL; ++s) {
@@ -449,14 +473,7 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_bwd_general_kernel(
             }
 #pragma unroll
             for (int s = 0; s < KPL; ++s) {
-                const float ds = (masked[s] || s * kWave + lane >= Ks) ? 0.f : dv[s];
-                if (p.cosine) {
-                    alpha[s] = ds / (nq * np_[s]);
-                    beta[s] = (np_[s] > kEps) ? ds * sim[s] / (np_[s] * np_[s]) : 0.f;
-                    gamma += (nq > kEps) ? ds * sim[s] / (nq * nq) : 0.f;
-                } else {
-                    alpha[s] = ds;
-                }
+                through_similarity(s, (masked[s] || s * kWave + lane >= Ks) ? 0.f : dv[s]);
             }
         }
 #pragma unroll
@@ -583,6 +600,16 @@ int et_epipolar_backward_general(const EtLayerDesc *desc, const float *xs, const
                                  const float *prior, const float *grad_out, int c_sim, int c_val, int flags, float *grad_q,
                                  float *grad_map_sim, float *grad_map_val, float *grad_prior, void *stream)
 {
+    return et_epipolar_backward_general_ga(desc, xs, ys, steps, cam, q, map_sim, map_val, prior, grad_out, nullptr, c_sim, c_val, flags,
+                                           grad_q, grad_map_sim, grad_map_val, grad_prior, stream);
+}
+
+int et_epipolar_backward_general_ga(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                                    const float *cam, const float *q, const float *map_sim, const float *map_val,
+                                    const float *prior, const float *grad_out, const float *grad_attn, int c_sim, int c_val,
+                                    int flags, float *grad_q, float *grad_map_sim, float *grad_map_val, float *grad_prior,
+                                    void *stream)
+{
     if (!desc) return fail("et_epipolar_backward_general: desc is NULL");
     EtLayerDesc chk = *desc;
     chk.C = 4;
@@ -612,7 +639,7 @@ int et_epipolar_backward_general(const EtLayerDesc *desc, const float *xs, const
     bp.f.attn_max = (flags & ET_GENERAL_ATTENTION_MAX) ? 1 : 0;
     bp.f.cosine = (flags & (ET_GENERAL_COSINE | ET_GENERAL_ATTENTION_MAX)) ? 1 : 0;
     bp.f.sim_prior = (flags & ET_GENERAL_SIM_PRIOR) ? 1 : 0;
-    bp.gout = grad_out; bp.gq = grad_q; bp.gsim = grad_map_sim; bp.gval = grad_map_val; bp.gprior = grad_prior;
+    bp.gout = grad_out; bp.gattn = grad_attn; bp.gq = grad_q; bp.gsim = grad_map_sim; bp.gval = grad_map_val; bp.gprior = grad_prior;
     const long long blocks = (hw * desc->N + kGenWaves - 1) / kGenWaves;
     if (blocks > 0x7fffffffLL) return fail("grid too large");
     const size_t lds = (size_t)kGenWaves * gen_bwd_wave_floats(desc->K) * sizeof(float);

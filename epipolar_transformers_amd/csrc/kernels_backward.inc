@@ -121,6 +121,12 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_kernel(con
         }
 
         // ---------------- soft-max gradient, lanes <-> samples -----------------
+        if (p.gattn) {  // block-uniform: d loss / d attn_k reaches a_k beside e_k = g . S_k (include/epipolar_amd.h)
+            const float *ga = p.gattn + (size_t)n * K * HW + pix;
+#pragma unroll
+            for (int s = 0; s < KPL; ++s)
+                if (s * kWave + lane < K) v_da[s] += ga[(size_t)(s * kWave + lane) * HW];
+        }
         float v_a[KPL], v_ds[KPL];
         if (d.softmax_enabled) {
             float mx = neg_inf;
@@ -339,6 +345,12 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_emit_kerne
         }
 
         // ---------------- soft-max gradient, lanes <-> samples -----------------------
+        if (p.gattn) {  // block-uniform: d loss / d attn_k reaches a_k beside e_k = g . S_k (include/epipolar_amd.h)
+            const float *ga = p.gattn + (size_t)n * K * HW + pix;
+#pragma unroll
+            for (int s = 0; s < KPL; ++s)
+                if (s * kWave + lane < K) v_da[s] += ga[(size_t)(s * kWave + lane) * HW];
+        }
         float v_a[KPL], v_ds[KPL];
         if (d.softmax_enabled) {
             float mx = neg_inf;

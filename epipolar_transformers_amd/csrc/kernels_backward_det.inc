@@ -13,7 +13,10 @@
 // Bs[p, u] = sum_k ds_k w_ku, ds_k = scale a_k (e_k - sum_j a_j e_j)  ->  |Bs| <= 2 |scale| max_k |e_k|;  e_k = g . S_k with S_k a
 // convex combination of source rows  ->  |e_k| <= 256 M_g M_src.  So
 //     |c| <= 32 (2 |scale| 256 M_g M_src M_ref + M_g) = bound        (M_* = max |.| of the pair's three maps; x (1 + 1/64) for
-// the rounding of the split-fp16 products).  The forms the tile path admits: merged and the half-array form add c once per group
+// the rounding of the split-fp16 products).  With a gradient ga = d loss / d attn the soft-max gradient is formed from e_k + ga_k,
+// |e_k + ga_k| <= 256 M_g M_src + M_ga (M_ga = max |ga| of the pair), and the bound becomes
+//     32 (2 |scale| (256 M_g M_src + M_ga) M_ref + M_g)              -- the same bits as above for M_ga = 0, and a proper bound
+// (not 0) for a loss on the attention alone (M_g = 0).  The forms the tile path admits: merged and the half-array form add c once per group
 // run and (row, channel); a single source role adds one of the two terms; the two-round form of the 256-row kernel (one
 // role, or ET_VARIANT_TILE_CLASSIC) adds the Bs term and the B term SEPARATELY -- two additions per group run, each bounded by its
 // own term, their magnitudes together by `bound`.  What counts is the sum of magnitudes: a group run of m pixels is bounded by
@@ -34,10 +37,12 @@ struct DetQuantum {
     float q, invq, bound;
 };
 
-__host__ __device__ inline DetQuantum det_quantum(float softmax_scale, float m_ref, float m_src, float m_g)
+__host__ __device__ inline DetQuantum det_quantum(float softmax_scale, float m_ref, float m_src, float m_g, float m_ga = 0.f)
 {
-    const double b = 32.0 * (2.0 * fabs((double)softmax_scale) * 256.0 * (double)m_g * (double)m_src * (double)m_ref + (double)m_g) *
-                     (1.0 + 1.0 / 64.0);
+    // (the M_ga term is a separate addend: with M_ga = 0 the sum is the expression without it, bit for bit -- whatever M_ref is)
+    const double s2 = 2.0 * fabs((double)softmax_scale);
+    const double ga_term = m_ga > 0.f ? s2 * (double)m_ga * (double)m_ref : 0.0;
+    const double b = 32.0 * ((s2 * 256.0 * (double)m_g * (double)m_src * (double)m_ref + ga_term) + (double)m_g) * (1.0 + 1.0 / 64.0);
     DetQuantum r;
     r.bound = (float)b;                 // (the exponent is taken from the fp32 value: what the caller is told is what q is made for)
     r.q = r.invq = 1.f;
@@ -54,17 +59,23 @@ __host__ __device__ inline DetQuantum det_quantum(float softmax_scale, float m_r
     return r;
 }
 
-// max |.| of the three maps of every pair: block (b, n) takes every gridDim.x-th run of 256 float4 of pair n and leaves
-// { M_ref, M_src, M_g, 0 } in partial[(n * gridDim.x + b) * 4 ..] (fmaxf: a NaN is skipped -- it trips the guard later)
+// max |.| of the three maps of every pair (and of its rows of gattn = d loss / d attn, nullable: K H W floats per pair): block
+// (b, n) takes every gridDim.x-th run of 256 float4 of pair n and leaves { M_ref, M_src, M_g, M_ga } in
+// partial[(n * gridDim.x + b) * 4 ..] (fmaxf: a NaN is skipped -- it trips the guard later)
 __global__ __launch_bounds__(256) void det_maxima_kernel(const float4 *__restrict__ fref, const float4 *__restrict__ fsrc,
                                                          const float4 *__restrict__ gout, unsigned vec4_per_pair,
+                                                         const float *__restrict__ gattn, unsigned ga_per_pair,
                                                          float *__restrict__ partial)
 {
-    __shared__ float s_m[3][4];
+    __shared__ float s_m[4][4];
     const int n = blockIdx.y;
     const size_t base = (size_t)n * vec4_per_pair;
     auto amax4 = [](float m, const float4 &v) { return fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w))); };
-    float m0 = 0.f, m1 = 0.f, m2 = 0.f;
+    float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f;
+    if (gattn) {    // (scalar loads: K H W need not be a multiple of four)
+        const float *ga = gattn + (size_t)n * ga_per_pair;
+        for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < ga_per_pair; i += gridDim.x * blockDim.x) m3 = fmaxf(m3, fabsf(ga[i]));
+    }
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < vec4_per_pair; i += gridDim.x * blockDim.x) {
         const float4 a = fref[base + i], b = fsrc[base + i], c = gout[base + i];
         m0 = amax4(m0, a);
@@ -74,17 +85,18 @@ __global__ __launch_bounds__(256) void det_maxima_kernel(const float4 *__restric
     m0 = wave_max(m0);
     m1 = wave_max(m1);
     m2 = wave_max(m2);
+    m3 = wave_max(m3);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         s_m[0][wave] = m0;
         s_m[1][wave] = m1;
         s_m[2][wave] = m2;
+        s_m[3][wave] = m3;
     }
     __syncthreads();
     if (threadIdx.x < 4) {
         const int t = threadIdx.x;
-        partial[((size_t)n * gridDim.x + blockIdx.x) * 4 + t] =
-            t < 3 ? fmaxf(fmaxf(s_m[t][0], s_m[t][1]), fmaxf(s_m[t][2], s_m[t][3])) : 0.f;
+        partial[((size_t)n * gridDim.x + blockIdx.x) * 4 + t] = fmaxf(fmaxf(s_m[t][0], s_m[t][1]), fmaxf(s_m[t][2], s_m[t][3]));
     }
 }
 
@@ -94,10 +106,10 @@ __global__ __launch_bounds__(64) void det_quantum_kernel(int N, int blocks_per_p
 {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
-    float m[3] = {0.f, 0.f, 0.f};
+    float m[4] = {0.f, 0.f, 0.f, 0.f};
     for (int b = 0; b < blocks_per_pair; ++b)
-        for (int t = 0; t < 3; ++t) m[t] = fmaxf(m[t], partial[((size_t)n * blocks_per_pair + b) * 4 + t]);
-    const DetQuantum r = det_quantum(softmax_scale, m[0], m[1], m[2]);
+        for (int t = 0; t < 4; ++t) m[t] = fmaxf(m[t], partial[((size_t)n * blocks_per_pair + b) * 4 + t]);
+    const DetQuantum r = det_quantum(softmax_scale, m[0], m[1], m[2], m[3]);
     *reinterpret_cast<float4 *>(quanta + (size_t)n * 4) = make_float4(r.q, r.invq, r.bound, 0.f);
 }
 

@@ -5,7 +5,7 @@
 // which is reused four times.  With g = d(out), f = feat_ref rows, F2_U the tile's source rows:
 //
 //   D = F1_t . F2_U^T          -> sim[p,k]   (resampled, kept in registers)
-//   E = G_t  . F2_U^T          -> e[p,k] = g . S_k    (the array now holds E)
+//   E = G_t  . F2_U^T          -> e[p,k] = g . S_k    (the array now holds E)  [+ ga[p,k] = d loss / d attn, where given]
 //   soft-max forward + backward, lanes <-> samples:  a[p,k],  ds[p,k] = d(sim)
 //   Bs[p,u] = sum ds w   (array)  -> d(feat_ref)_t  = Bs . F2_U            (as the forward's second GEMM)
 //                                   d(feat_src)_U += Bs^T . F1_t           ('other1', similarity path)
@@ -541,8 +541,11 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
         // With the forward's attention a (what autograd saves in the reference too) the soft-max backward needs no
         // logits: ds_k = scale a_k (e_k - sum_j a_j e_j) is already zero where the mask put -1e10 (a_k = 0 exactly);
         // only a pixel whose samples are ALL masked (an all-zero reference row: uniform attention) has to be told
-        // apart -- every a_k the same value 1 / K.  (All logits equal without a mask also gives that, and then
-        // e_k - dot = 0 unless the samples differ while their logits agree to the last bit.)
+        // apart -- every a_k the same value 1 / K.  (All logits equal without a mask also gives that.  Without grad_attn
+        // e_k - dot = 0 then, unless the samples differ while their logits agree to the last bit.  With grad_attn the true
+        // ds_k = scale / K (ga_k - mean ga) of such an unmasked pixel is NOT zero and this branch drops it, where the
+        // recomputed-attention branch, which sees the mask itself, keeps it: a documented limit of the saved-attention
+        // form, include/epipolar_amd.h.)
         const bool have_attn = tp.attn != nullptr;
         float simv[PW][KPL];       // recomputed logits, or the forward's attention
         if (!have_attn) {
@@ -576,6 +579,14 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
         // ================= 2. E = G . F2_U^T, e = resample(E); soft-max forward and backward =================
         const bool rows_passed_guard = gemm_rows(gout);      // block-uniform
         __syncthreads();
+        // d loss / d attn (nullable, (N,K,H,W) as the saved attention): it reaches a_k beside e_k, so e_k + ga_k takes e_k's place
+        // in the soft-max gradient below -- one load per (pixel, sample), added where e is produced
+        const bool have_ga = p.gattn != nullptr;             // block-uniform
+        auto ga_at = [&](int i, int k) {
+            const __amdgpu_buffer_rsrc_t gbuf = make_rsrc(p.gattn + (size_t)n * K * HW, (unsigned)K * HW * 4u);
+            const int pix = __builtin_amdgcn_readfirstlane(s_pix[i]);
+            return buf_load_f1(gbuf, (active(i) && k < K) ? (k * HW + pix) * 4 : 0x7ffff000, 0);   // (else: zeros)
+        };
         float av[PW][KPL], dsv[PW][KPL];
         if constexpr (KPL == 1) {   // four pixels at a time: interleaved wave reductions
 #pragma unroll
@@ -590,6 +601,7 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
                 float wt[4];
                 derive(i, 0, active(i), sl, wt);
                 ev[j] = resample(s_D + i * kTileStride, sl, wt);
+                if (have_ga) ev[j] += ga_at(i, lane);
                 masked[j] = simv[i0 + j][0] == 0.f;
                 const float l = masked[j] ? -1e10f : simv[i0 + j][0];               // epipolar.py:298
                 lg[j] = d.softmax_enabled ? l * d.softmax_scale : l / (float)K;   // epipolar.py:306 / 311
@@ -644,6 +656,7 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
                 float wt[4];
                 derive(i, s, active(i), sl, wt);
                 ev[s] = resample(s_D + i * kTileStride, sl, wt);
+                if (have_ga) ev[s] += ga_at(i, s * kWave + lane);
                 masked[s] = simv[ii][s] == 0.f;
                 const float l = masked[s] ? -1e10f : simv[ii][s];                  // epipolar.py:298
                 lg[s] = d.softmax_enabled ? l * d.softmax_scale : l / (float)K;   // epipolar.py:306 / 311

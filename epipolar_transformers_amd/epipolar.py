@@ -335,7 +335,7 @@ class Epipolar(nn.Module):
             prior = torch.stack([self.prior[(int(a), int(b))].to(q) for a, b in zip(camera, other_camera)])
         mode = dict(prior_mul=bool(prior is not None and e.PRIORMUL and not sim_prior), cosine=cos, attention_max=is_max,
                     sim_prior=sim_prior)
-        return ops.GeneralAttend.apply(q, m1, m2, cam, self.layer_spec(), bool(e.POOLING), prior, mode)
+        return ops.GeneralAttend.apply(q, m1, m2, cam, self.layer_spec(), bool(e.POOLING), prior, mode, self._attn_grad())
 
     def _attend_general_chunk(self, feat1, feat2, P1, P2, camera=None, other_camera=None, ref1=None, ref2=None):
         """The operator's non-headline branches, restated op for op from epipolar.py:131-247 and
@@ -443,7 +443,12 @@ class Epipolar(nn.Module):
     def attend(self, feat1, feat2, P1, P2):
         """The fused kernel only: (out, attn, corr_pos), `out` before the z branch."""
         cam = self._cam(P1, P2, feat1.device)
-        return ops.EpipolarAttend.apply(feat1, feat2, cam, self.layer_spec())
+        return ops.EpipolarAttend.apply(feat1, feat2, cam, self.layer_spec(), self._attn_grad())
+
+    def _attn_grad(self) -> bool:
+        """EPIPOLAR_AMD.ATTN_GRAD: the returned attention (`depth`) is a differentiable output of the HIP attend functions, as it
+        is in the reference (epipolar.py:245, 263).  Off by default: callers take `.numpy()` of that return with autograd on."""
+        return bool(amd_knob(self.cfg, "ATTN_GRAD", False))
 
     def _folded_z(self):
         """Eval-mode algebra of epipolar.py:250-253: bn(z(out)) [+ out] == out @ Wf^T + bf with

@@ -214,13 +214,27 @@ def forward_general_nhwc(spec: LayerSpec, q: torch.Tensor, map_sim: torch.Tensor
     return out, attn, corr
 
 
+def _require_grad_attn(grad_attn, shape, device):
+    """`grad_attn`: None, or d loss / d attn -- float32 of the attention's shape on `device`; returned contiguous."""
+    if grad_attn is None:
+        return None
+    _require_gpu(grad_attn, "grad_attn")
+    if tuple(grad_attn.shape) != tuple(shape) or grad_attn.device != device:
+        raise ValueError("grad_attn must be a float32 %s tensor on %s, got %s on %s" %
+                         (tuple(shape), device, tuple(grad_attn.shape), grad_attn.device))
+    return grad_attn.contiguous()
+
+
 def backward_general_nhwc(spec: LayerSpec, q, map_sim, map_val, cam, grad_out, pooling=False, need_sim=True, need_val=True,
-                          prior=None, prior_mul=False, cosine=False, attention_max=False, sim_prior=False, need_prior=False):
+                          prior=None, prior_mul=False, cosine=False, attention_max=False, sim_prior=False, need_prior=False,
+                          grad_attn=None):
     """Backward of forward_general_nhwc, every branch: returns (grad_q, grad_map_sim | None, grad_map_val | None,
     grad_prior | None), NHWC maps, grad_prior (N,K',H,W).  The map gradients are accumulated with float atomics
-    (reproducible to rounding only)."""
+    (reproducible to rounding only).  `grad_attn`: d loss / d attn (N,K',H,W) or None -- the gradient through the returned
+    attention (et_epipolar_backward_general_ga)."""
     n, h, w, cs, cv, ks = _require_general(spec, q, map_sim, map_val, cam, prior, pooling)
     _require_f32(grad_out, "grad_out", q.device, (n, h, w, cv), "grad_out must be a contiguous (N,H,W,Cv) tensor")
+    grad_attn = _require_grad_attn(grad_attn, (n, ks, h, w), q.device)
     xs, ys, steps = spec.constants(q.device)
     gq = _empty(None, like=q)
     gsim = torch.zeros_like(map_sim) if need_sim else None
@@ -228,30 +242,33 @@ def backward_general_nhwc(spec: LayerSpec, q, map_sim, map_val, cam, grad_out, p
     gprior = _empty(None, like=prior) if (need_prior and prior is not None) else None
     d = spec.desc(n, 4)
     flags = _general_flags(pooling, prior_mul, cosine, attention_max, sim_prior)
-    _call("et_epipolar_backward_general", q, ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(q), _ptr(map_sim),
-          _ptr(map_val), _ptr(prior), _ptr(grad_out), cs, cv, flags, _ptr(gq), _ptr(gsim), _ptr(gval), _ptr(gprior), _stream(q))
+    _call("et_epipolar_backward_general_ga", q, ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(q), _ptr(map_sim),
+          _ptr(map_val), _ptr(prior), _ptr(grad_out), _ptr(grad_attn), cs, cv, flags, _ptr(gq), _ptr(gsim), _ptr(gval), _ptr(gprior),
+          _stream(q))
     return gq, gsim, gval, gprior
 
 
 class GeneralAttend(torch.autograd.Function):
     """The operator's non-headline branches with autograd (every one since ABI 12): logical NCHW in and out, `prior` the
-    (N,K',H,W) stack of the pairs' prior tables or None; `attn` and `corr_pos` without gradient (as EpipolarAttend).
-    `mode`: dict(pooling, prior_mul, cosine, attention_max, sim_prior) of bools."""
+    (N,K',H,W) stack of the pairs' prior tables or None; `corr_pos` without gradient, `attn` too unless `attn_grad` (as
+    EpipolarAttend).  `mode`: dict(pooling, prior_mul, cosine, attention_max, sim_prior) of bools."""
 
     @staticmethod
-    def forward(ctx, q, map_sim, map_val, cam, spec: LayerSpec, pooling, prior=None, mode=None):
+    def forward(ctx, q, map_sim, map_val, cam, spec: LayerSpec, pooling, prior=None, mode=None, attn_grad: bool = False):
         mode = dict(mode or {}, pooling=bool(pooling))
         qn, m1, m2 = to_nhwc(q), to_nhwc(map_sim), to_nhwc(map_val)
         pr = None if prior is None else prior.contiguous()
         out, attn, corr = forward_general_nhwc(spec, qn, m1, m2, cam, prior=pr, **mode)
         ctx.spec, ctx.mode, ctx.has_prior = spec, mode, pr is not None
         ctx.save_for_backward(*((qn, m1, m2, cam) + ((pr,) if pr is not None else ())))
-        ctx.mark_non_differentiable(attn, corr)
+        _mark_attention(ctx, attn, corr, attn_grad)
         return out.permute(0, 3, 1, 2), attn, corr
 
     @staticmethod
-    def backward(ctx, grad_out, _ga, _gc):
+    def backward(ctx, grad_out, grad_attn, _gc):
         qn, m1, m2, cam = ctx.saved_tensors[:4]
+        if grad_out is None:                # (attn_grad: a loss on the attention alone)
+            grad_out = torch.zeros_like(m2).permute(0, 3, 1, 2)
         pr = ctx.saved_tensors[4] if ctx.has_prior else None
         if (ctx.spec.variant & _lib.ET_VARIANT_BWD_DETERMINISTIC) and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
             raise RuntimeError("EPIPOLAR_AMD.DETERMINISTIC: the option branches (theta / phi / g, POOLING, PRIOR, cosine, ATTENTION max, "
@@ -260,9 +277,24 @@ class GeneralAttend(torch.autograd.Function):
                                "deterministic backward")
         gq, gs, gv, gp = backward_general_nhwc(ctx.spec, qn, m1, m2, cam, to_nhwc(grad_out), need_sim=ctx.needs_input_grad[1],
                                                need_val=ctx.needs_input_grad[2], prior=pr,
-                                               need_prior=ctx.has_prior and ctx.needs_input_grad[6], **ctx.mode)
+                                               need_prior=ctx.has_prior and ctx.needs_input_grad[6],
+                                               grad_attn=grad_attn if ctx.attn_grad else None,
+                                               **ctx.mode)
         nchw = lambda t: None if t is None else t.permute(0, 3, 1, 2)
-        return nchw(gq) if ctx.needs_input_grad[0] else None, nchw(gs), nchw(gv), None, None, None, gp, None
+        return nchw(gq) if ctx.needs_input_grad[0] else None, nchw(gs), nchw(gv), None, None, None, gp, None, None
+
+
+def _mark_attention(ctx, attn, corr, attn_grad: bool):
+    """Which of the two side outputs of the attend functions carry gradient.  Default: neither.  `attn_grad`: the attention does
+    (the reference's `depth` is an ordinary autograd tensor, epipolar.py:245, 263) -- and gradients are no longer materialised,
+    so that an attention nobody differentiated arrives in backward as None (today's path, no zero tensor) and a loss on the
+    attention alone hands a None grad_out (replaced by zeros there)."""
+    ctx.attn_grad = bool(attn_grad)         # (backward reads grad_attn only then: a non-differentiable output's is zeros or None)
+    if attn_grad:
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(corr)
+    else:
+        ctx.mark_non_differentiable(attn, corr)
 
 
 _TILE_BITS = (_lib.ET_VARIANT_TILE_SPLIT | _lib.ET_VARIANT_TILE_CLASSIC |
@@ -561,7 +593,8 @@ def _default_backward_form(spec: LayerSpec, tile_bytes: int, use_workspace: bool
     return form
 
 
-def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, form=None, attn=None, workspace=None):
+def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, form=None, attn=None, workspace=None,
+                  grad_attn=None):
     """d(feat_ref), d(feat_src) of forward_nhwc.  Four forms of the same gradient:
       "tile"    MFMA tile formulation, d(feat_src) accumulated with float atomics across tiles: fastest,
                 reproducible to rounding only (C == 256, K <= 256);
@@ -575,7 +608,9 @@ def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, 
     (_default_backward_form).  `attn`: the attention forward_nhwc returned for the same inputs
     (N,K,H,W) -- the tile form then does not recompute the soft-max (one GEMM of five less); the other forms ignore it.
     `workspace`: a caller-owned uint8 tensor for the "tile" / "gather" form instead of the cached one (the tile form's has
-    the forward's layout and size: tile_workspace)."""
+    the forward's layout and size: tile_workspace).
+    `grad_attn`: d loss / d attn (N,K,H,W) or None -- the gradient through the returned attention, in every form (the *_ga
+    entry points: e_k + ga_k in place of e_k = grad_out . S_k in the soft-max gradient)."""
     n, h, w, c = _require_pair(spec, ref, src, cam)
     _require_gpu(grad_out, "grad_out")
     if grad_out.shape != ref.shape or grad_out.device != ref.device:
@@ -583,6 +618,7 @@ def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, 
                          (tuple(ref.shape), ref.device, tuple(grad_out.shape), grad_out.device))
     xs, ys, steps = spec.constants(ref.device)
     grad_out = grad_out.contiguous()
+    grad_attn = _require_grad_attn(grad_attn, (n, spec.K, h, w), ref.device)
     g_ref = _empty(None, like=ref)
     g_src = _empty(None, like=src)
     d = spec.desc(n, c)
@@ -592,7 +628,7 @@ def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, 
         form = _default_backward_form(spec, tile_bytes, use_workspace)
     if form not in ("tile", "tile_det", "gather", "atomic"):
         raise ValueError("unknown backward form %r" % (form,))
-    args = (ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(ref), _ptr(src), _ptr(grad_out),
+    args = (ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(ref), _ptr(src), _ptr(grad_out), _ptr(grad_attn),
             _ptr(g_ref), _ptr(g_src))
     if form in ("tile", "tile_det"):
         det = form == "tile_det"
@@ -604,7 +640,7 @@ def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, 
         if attn is not None:
             _require_f32(attn, "attn", ref.device, (n, spec.K, h, w))
         # (the attention form of the float tile backward is handed the bytes it asked for, the deterministic form all it may use)
-        _call("et_epipolar_backward_tiled_det" if det else "et_epipolar_backward_tiled_attn", ref, *args[:7], _ptr(attn), *args[7:],
+        _call("et_epipolar_backward_tiled_det_ga" if det else "et_epipolar_backward_tiled_ga", ref, *args[:7], _ptr(attn), *args[7:],
               _ptr(ws), ctypes.c_size_t(ws.numel() if det else tile_bytes), _stream(ref))
         if det and POISON_OUTPUTS:          # (test suite: the guard bit surfaces at the call that set it)
             check_tile_errors(workspace=ws)
@@ -613,7 +649,7 @@ def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, 
         if form == "gather":
             ws_bytes = int(lib.et_epipolar_backward_workspace_bytes(ctypes.byref(d)))
             ws = _own_workspace(workspace, ws_bytes, ref.device, "bwd")
-        _call("et_epipolar_backward", ref, *args, _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(ref))
+        _call("et_epipolar_backward_ga", ref, *args, _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(ref))
     return g_ref, g_src
 
 
@@ -782,26 +818,28 @@ class EpipolarAttend(torch.autograd.Function):
     samples of f_src on the pixel's epipolar segment (epipolar.py:188-247).
     Inputs/outputs are logical NCHW; attn and corr_pos are returned without
     gradient (the reference never back-propagates through them in the
-    configurations of BASELINE.json).  The backward takes backward_nhwc's default form: the MFMA tile kernel for
+    configurations of BASELINE.json) -- unless `attn_grad`: then attn is an ordinary
+    differentiable output, as in the reference (epipolar.py:245, 263), and its gradient
+    goes into the same HIP backward (backward_nhwc's grad_attn).  The backward takes backward_nhwc's default form: the MFMA tile kernel for
     the 256-channel head (float atomics across tiles, reproducible to rounding; with ET_VARIANT_BWD_DETERMINISTIC in the spec's
     variant -- EPIPOLAR_AMD.DETERMINISTIC -- its bit-reproducible integer-sum form), the bit-reproducible gather form
     otherwise or when the spec's variant carries ET_VARIANT_NO_TILE."""
 
     @staticmethod
-    def forward(ctx, feat_ref, feat_src, cam, spec: LayerSpec):
+    def forward(ctx, feat_ref, feat_src, cam, spec: LayerSpec, attn_grad: bool = False):
         ref = to_nhwc(feat_ref)
         src = to_nhwc(feat_src)
         out, attn, corr = forward_nhwc(spec, ref, src, cam)
         ctx.spec = spec
         ctx.save_for_backward(ref, src, cam, attn)       # (the soft-max output, as autograd keeps it in the reference)
-        ctx.mark_non_differentiable(attn, corr)
+        _mark_attention(ctx, attn, corr, attn_grad)
         return out.permute(0, 3, 1, 2), attn, corr
 
     @staticmethod
-    def backward(ctx, grad_out, _ga, _gc):
+    def backward(ctx, grad_out, grad_attn, _gc):
         ref, src, cam, attn = ctx.saved_tensors
-        g = to_nhwc(grad_out)
-        g_ref, g_src = backward_nhwc(ctx.spec, ref, src, cam, g, attn=attn)
+        g = torch.zeros_like(ref) if grad_out is None else to_nhwc(grad_out)     # (None: attn_grad, a loss on the attention alone)
+        g_ref, g_src = backward_nhwc(ctx.spec, ref, src, cam, g, attn=attn, grad_attn=grad_attn if ctx.attn_grad else None)
         need_ref, need_src = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         return (g_ref.permute(0, 3, 1, 2) if need_ref else None,
-                g_src.permute(0, 3, 1, 2) if need_src else None, None, None)
+                g_src.permute(0, 3, 1, 2) if need_src else None, None, None, None)

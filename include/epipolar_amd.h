@@ -30,6 +30,9 @@ extern "C" {
 #endif
 
 #define ET_ABI_VERSION 14
+/* The *_ga entry points (gradient through the returned attention) were added without touching an existing signature, so the
+ * version stays; a caller tests for them with this macro. */
+#define ET_HAS_ATTN_GRAD 1
 
 /* Static description of one layer call: the cfg keys the reference reads in
  * Epipolar.__init__ (epipolar.py:12-54) and at call time (epipolar.py:303-311,
@@ -213,11 +216,25 @@ int et_epipolar_forward_general(const EtLayerDesc *desc, const float *xs, const 
  * the gradient of POOLING's per-channel maximum goes to the sample that won (the first on a tie, as torch.max); cosine
  * similarity is differentiated as torch does (through the unclamped norms); ATTENTION max passes grad_out to the first
  * arg-max sample of map_val only (grad_q = 0, nothing into map_sim); SIMILARITY prior: grad_prior_k' = grad_out . V_k'.
- * Gradients through the `attn` / `corr_pos` outputs are not provided (the reference configurations never use them). */
+ * `corr_pos` carries no gradient (an arg-max location).
+ *
+ * et_epipolar_backward_general_ga: the same with grad_attn = d loss / d attn, nullable, (N,K',H,W) -- the returned attention is an
+ * ordinary differentiable output in the reference (epipolar.py:245, 263).  With e_k' = grad_out . V_k' and ga_k' = grad_attn:
+ *   ATTENTION avg, every similarity and prior: e_k' + ga_k' takes the place of e_k' everywhere -- the soft-max receives it (times
+ *     prior_k' under PRIOR_MUL, where grad_prior_k' = softmax_k' (e_k' + ga_k')); soft-max off: d sim_k' = (e_k' + ga_k') / K'; zero
+ *     under the `sim == 0` mask either way; SIMILARITY prior: grad_prior_k' = e_k' + ga_k';
+ *   ATTENTION max: the attention is the raw cosine, so d sim_k' = ga_k' (no mask) goes through the cosine derivative into grad_q
+ *     and grad_map_sim (both zero without grad_attn); with SIM_PRIOR beside it grad_prior_k' = ga_k'.  The value gradient is unchanged.
+ * grad_out stays required (a loss on the attention alone passes zeros); grad_attn NULL = et_epipolar_backward_general, bit for bit. */
 int et_epipolar_backward_general(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
                                  const float *cam, const float *q, const float *map_sim, const float *map_val,
                                  const float *prior, const float *grad_out, int c_sim, int c_val, int flags, float *grad_q,
                                  float *grad_map_sim, float *grad_map_val, float *grad_prior, void *stream);
+int et_epipolar_backward_general_ga(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                                    const float *cam, const float *q, const float *map_sim, const float *map_val,
+                                    const float *prior, const float *grad_out, const float *grad_attn, int c_sim, int c_val,
+                                    int flags, float *grad_q, float *grad_map_sim, float *grad_map_val, float *grad_prior,
+                                    void *stream);
 
 /* Backward of et_epipolar_forward w.r.t. both feature maps (sample locations
  * carry no gradient, epipolar.py:178-183).  Everything is recomputed from the
@@ -237,6 +254,21 @@ int et_epipolar_backward(const EtLayerDesc *desc, const float *xs, const float *
                          const float *cam, const float *feat_ref, const float *feat_src,
                          const float *grad_out, float *grad_ref, float *grad_src, void *workspace,
                          size_t workspace_bytes, void *stream);
+
+/* Gradient through the returned attention (ET_HAS_ATTN_GRAD): every backward of the headline operator in a second form that
+ * also takes grad_attn = d loss / d attn, nullable, (N,K,H,W) float32 -- `attn` is an ordinary differentiable output in the
+ * reference (epipolar.py:245, 263).  With a = attn, e_k = grad_out . S_k and ga = grad_attn, the gradient reaching a_k through
+ * out = sum_k a_k S_k and through the attention itself is e_k + ga_k:
+ *     soft-max on :  d sim_k = softmax_scale a_k ((e_k + ga_k) - sum_j a_j (e_j + ga_j)),   0 under the `sim == 0` mask
+ *     soft-max off:  d sim_k = (e_k + ga_k) / K   (a = sim / K),                             0 under the mask
+ * and everything behind d sim_k (grad_ref, the similarity part of grad_src) is as without it; the value part of grad_src,
+ * a_k grad_out into the samples, does not involve ga.  grad_out stays required: a loss on the attention alone passes zeros.
+ * With grad_attn NULL each is the entry point without _ga, bit for bit (those call these).  Workspaces: as for the forms
+ * without _ga, same sizes and layouts. */
+int et_epipolar_backward_ga(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                            const float *cam, const float *feat_ref, const float *feat_src,
+                            const float *grad_out, const float *grad_attn, float *grad_ref, float *grad_src, void *workspace,
+                            size_t workspace_bytes, void *stream);
 
 /* The backward in the same MFMA tile formulation (C == 256, K <= 256): per 32-pixel tile the similarity and
  * g.S_k come from two GEMMs against the tile's source rows, d(feat_ref) from a third, and d(feat_src) from
@@ -258,6 +290,15 @@ int et_epipolar_backward_tiled_attn(const EtLayerDesc *desc, const float *xs, co
                                     const float *cam, const float *feat_ref, const float *feat_src,
                                     const float *attn, const float *grad_out, float *grad_ref, float *grad_src,
                                     void *workspace, size_t workspace_bytes, void *stream);
+/* ... and with grad_attn (see et_epipolar_backward_ga); attn and grad_attn each nullable.  One limit with BOTH given and the
+ * soft-max on: the kernel knows the all-masked pixel (zero reference row) from its attention alone, every a_k = 1 / K, and gives
+ * it d sim = 0.  An UNMASKED pixel whose logits all agree to the last bit (a constant source region, vanishing features) has
+ * the same attention, and its true d sim_k = softmax_scale / K (ga_k - mean_j ga_j) is dropped as well; without grad_attn that
+ * term is zero anyway.  With attn NULL the kernel recomputes the logits, sees the mask itself and keeps the term. */
+int et_epipolar_backward_tiled_ga(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                                  const float *cam, const float *feat_ref, const float *feat_src, const float *attn,
+                                  const float *grad_out, const float *grad_attn, float *grad_ref, float *grad_src,
+                                  void *workspace, size_t workspace_bytes, void *stream);
 
 /* The tiled backward, BIT-REPRODUCIBLE (ABI 14): the same tiles and GEMMs, but the U x C results are not added into grad_src with
  * float atomics.  Each is scaled by 1 / q -- q one power of two per pair, derived from a BOUND on a contribution,
@@ -276,13 +317,24 @@ int et_epipolar_backward_tiled_attn(const EtLayerDesc *desc, const float *xs, co
  *               the results of that call are invalid.
  * Fails (et_last_error) with the soft-max off (the "attention" sim / K has no bound: et_epipolar_backward with a workspace is the
  * bit-reproducible form there), on a workspace that is too small, and where the tile path does not apply.
- * et_debug_host_det_quantum: HOST test hook, no GPU -- q and the bound for given maxima (desc: softmax_scale). */
+ * et_debug_host_det_quantum: HOST test hook, no GPU -- q and the bound for given maxima (desc: softmax_scale).
+ * et_epipolar_backward_tiled_det_ga: with grad_attn (see et_epipolar_backward_ga).  |e_k + ga_k| <= 256 M_g M_src + M_ga, M_ga =
+ * max |grad_attn| of the pair (taken in the pass that takes the other maxima; it lives in the maxima region: the workspace size
+ * does not change), so the bound is
+ *     32 (2 |softmax_scale| (256 M_g M_src + M_ga) M_ref + M_g) (1 + 1/64)
+ * -- the bits above for M_ga = 0, and a proper quantum for a loss on the attention alone (M_g = 0, M_ga > 0).
+ * et_debug_host_det_quantum_ga: the host hook with m_ga. */
 size_t et_epipolar_backward_tiled_det_workspace_bytes(const EtLayerDesc *desc);
 int et_epipolar_backward_tiled_det(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
                                    const float *cam, const float *feat_ref, const float *feat_src,
                                    const float *attn, const float *grad_out, float *grad_ref, float *grad_src,
                                    void *workspace, size_t workspace_bytes, void *stream);
 int et_debug_host_det_quantum(const EtLayerDesc *desc, float m_ref, float m_src, float m_g, float *q, float *bound);
+int et_epipolar_backward_tiled_det_ga(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                                      const float *cam, const float *feat_ref, const float *feat_src, const float *attn,
+                                      const float *grad_out, const float *grad_attn, float *grad_ref, float *grad_src,
+                                      void *workspace, size_t workspace_bytes, void *stream);
+int et_debug_host_det_quantum_ga(const EtLayerDesc *desc, float m_ref, float m_src, float m_g, float m_ga, float *q, float *bound);
 
 /* Residual fusion epilogue: x = feat + out + (y * scale[c] + shift[c])
  *   (epipolar.py:250-253 with ZRESIDUAL, then resnet.py:388 `ret + feat`),

@@ -32,7 +32,9 @@ def timed(fn, reps=10, warm=3):
     return (time.perf_counter() - t0) / reps * 1e3
 
 
-print("%s: backward tile %.3f ms, with the forward's attention %.3f ms" % (
+ga = torch.randn(128, K, H, H, device=dev, generator=g)      # d loss / d attn: one more (N,K,H,W) read
+print("%s: backward tile %.3f ms, with the forward's attention %.3f ms, with the attention and grad_attn %.3f ms" % (
     os.environ.get("EPIPOLAR_AMD_LIB", "product library"),
     timed(lambda: ops.backward_nhwc(spec, ref, src, cam, go, form="tile")),
-    timed(lambda: ops.backward_nhwc(spec, ref, src, cam, go, form="tile", attn=attn))))
+    timed(lambda: ops.backward_nhwc(spec, ref, src, cam, go, form="tile", attn=attn)),
+    timed(lambda: ops.backward_nhwc(spec, ref, src, cam, go, form="tile", attn=attn, grad_attn=ga))))
