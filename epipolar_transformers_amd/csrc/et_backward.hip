@@ -3,6 +3,7 @@
 
 namespace {
 #include "kernels_sample_table.inc"
+#include "kernels_pixel_phases.inc"
 #include "kernels_backward.inc"  // epipolar_bwd_kernel, epipolar_bwd_emit_kernel, bwd_scan/bucket, epipolar_bwd_gather_kernel
 
 template <int CPD, int KPL>

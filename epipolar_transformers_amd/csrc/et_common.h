@@ -4,16 +4,25 @@
 // Translation units (compiled in parallel by epipolar_transformers_amd/build.py, linked into one library):
 //   et_forward.hip        kernels_forward.inc        fused forward, any shape: one pixel per wave (epipolar_fwd_kernel)
 //                                                    and four pixels per wave in lockstep (epipolar_fwd_multi_kernel)
+//   et_forward_general.hip                           the parameterised / pooled / prior branches, forward and backward: one
+//                                                    wave per pixel, three maps (epipolar_fwd / bwd_general_kernel)
 //   et_forward_tile.hip   kernels_forward_tile.inc   C == 256 head, forward: reference pixels ordered by epipolar line,
 //                         kernels_forward_tile_ws.inc 32 per tile, two fp32 GEMMs per tile on the matrix cores with the
 //                                                    resampling / soft-max between them; persistent warp-specialised form
 //   et_backward.hip       kernels_backward.inc       backward, any shape: coefficient emission + scan / bucket / ordered
 //                                                    gather (no float atomics, bit-reproducible), float-atomic fallback
+//     both any-shape units: kernels_sample_table.inc a pixel's samples in registers: taps, weights, 2x2 tap cache bits
+//                         kernels_pixel_phases.inc   the phases their kernels share: soft-max gradient, arg-max, attn tile
 //   et_backward_tile.hip  kernels_backward_tile.inc  C == 256 head, backward in the same tile form
+//                         kernels_backward_det.inc   its bit-reproducible form: 64-bit integer sums for d(feat_src)
 //     both tile units:    kernels_tile_order.inc     the ordering of a tile call (sort keys, one bitonic sort per pair)
 //                         kernels_tile_common.inc    device helpers of both directions: taps, array rows, the tile GEMMs
 //                         et_tile_host.h             the host side of a tile call: checks, workspace, ordering, launch
+//   et_residual_gemm.hip  kernels_residual_gemm.inc  x = feat + bias + out . Wf^T as a split-fp16 GEMM, and the z branch's
+//                                                    batch statistics / backward (et_residual_gemm, et_z_*)
 //   et_misc.hip           kernels_misc.inc           sample_locs, residual epilogue, NCHW <-> NHWC, ABI version / errors
+//   et_wave_reduce.h                                 DPP wave reductions (wave_all_sum / max / min): general, tile, GEMM units
+//   et_split_f16.h                                   fp32 -> two fp16 halves for the matrix cores (tile units)
 //   epipolar_geometry.h                              bit-faithful float32 geometry (segment, sample set-up), host+device
 //
 // Common ideas:

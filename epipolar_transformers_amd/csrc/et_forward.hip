@@ -3,6 +3,7 @@
 
 namespace {
 #include "kernels_sample_table.inc"
+#include "kernels_pixel_phases.inc"
 #include "kernels_forward.inc"   // SampleTable, epipolar_fwd_kernel, epipolar_fwd_multi_kernel
 
 template <int CPL, int KPL>
@@ -58,14 +59,12 @@ int et_epipolar_forward(const EtLayerDesc *desc, const float *xs, const float *y
     const long long total = (long long)p.blocks_per_pair * desc->N;
     if (total > 0x7fffffffLL) return fail("grid too large");
     p.total_blocks = (int)total;
-    p.interleave = (desc->variant & ET_VARIANT_PIXEL_INTERLEAVE) ? 1 : 0;
     p.ablate = 0;
     const dim3 grid((unsigned)total);
-    const int kpl_ = (desc->K + 63) / 64;
-    const size_t lds = (attn ? (size_t)desc->K * kPixPerBlock * sizeof(float) : 0) +
-                       (size_t)kWavesPerBlock * kpl_ * kWave * 4 * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
     const int cpl = (desc->C + 255) / 256, kpl = (desc->K + 63) / 64;
+    const size_t lds = (attn ? (size_t)desc->K * kPixPerBlock * sizeof(float) : 0) +
+                       (size_t)kWavesPerBlock * kpl * kWave * 4 * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
     // variant 0 = the tuned default (measured on MI355X, profiles/): for the 256-channel head with K <= 64
     // four pixels per wave in lockstep; otherwise one pixel per wave, batches of 4 samples, <= 96 VGPRs (5 waves/SIMD),
     // waves of a block interleaved over neighbouring pixels

@@ -56,6 +56,138 @@ __device__ __forceinline__ float gen_sample(const float *map, int ch, int c, con
     return v;
 }
 
+// ---- the phases the forward and the backward kernel share ------------------------------------------------------------
+// Where a wave stands: its reference pixel, the pixel's epipolar segment, and the wave's arrays in LDS.
+struct GenPixel {
+    int n, pix;
+    et::Segment seg;
+    float4 *s_w;            // [K] bilinear weights
+    int4 *s_tap;            // [K] taps
+    float *s_sim;           // [K'] arrays from here on: one in the forward, three in the backward
+};
+
+// Wave -> (n, pix, h, w); lanes <-> samples: the epipolar segment, then every sample's taps and weights into LDS, fenced.
+// False for the waves behind the last pixel (wave-uniform: the kernels have no block-wide barrier).
+__device__ __forceinline__ bool gen_pixel(const GeneralParams &p, float *s_dyn, int wave_floats, int lane, GenPixel &px)
+{
+    const EtLayerDesc &d = p.d;
+    const int W = d.W, K = d.K, HW = d.H * W;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long gp = (long long)blockIdx.x * kGenWaves + wave;
+    px.n = (int)(gp / HW);
+    if (px.n >= d.N) return false;
+    px.pix = (int)(gp - (long long)px.n * HW);
+    const int h = px.pix / W, w = px.pix - h * W;
+    px.s_w = reinterpret_cast<float4 *>(s_dyn + (size_t)wave * wave_floats);
+    px.s_tap = reinterpret_cast<int4 *>(px.s_w + K);
+    px.s_sim = reinterpret_cast<float *>(px.s_tap + K);
+    px.seg = et::epipolar_segment(d, p.cam + (size_t)px.n * ET_CAM_STRIDE, p.xs[w], p.ys[h]);
+    for (int k = lane; k < K; k += kWave) {
+        const et::SampleSetup su = et::sample_setup(d, px.seg, p.steps[k]);
+        px.s_w[k] = make_float4(su.weight[0], su.weight[1], su.weight[2], su.weight[3]);
+        px.s_tap[k] = make_int4(su.tap[0], su.tap[1], su.tap[2], su.tap[3]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    return true;
+}
+
+// lanes <-> channels: the pixel's query row into registers; returns |q|^2 under the cosine similarity (else 0)
+__device__ __forceinline__ float gen_query(const GeneralParams &p, const float *qrow, int lane, float (&qv)[kGenMaxQ])
+{
+#pragma unroll
+    for (int i = 0; i < kGenMaxQ; ++i) qv[i] = (lane + i * kWave < p.cs) ? qrow[lane + i * kWave] : 0.f;
+    float qq = 0.f;
+    if (p.cosine) {
+#pragma unroll
+        for (int i = 0; i < kGenMaxQ; ++i) qq = fmaf(qv[i], qv[i], qq);
+        qq = wave_all_sum(qq);
+    }
+    return qq;
+}
+
+// taps and weights of similarity k': sample k, and under POOLING its partner k + K' (else sample k again)
+template <bool POOL>
+__device__ __forceinline__ void gen_taps(const int4 *s_tap, const float4 *s_w, int k, int Ks, int4 &t0, float4 &w0,
+                                         int4 &t1, float4 &w1)
+{
+    t0 = s_tap[k];
+    w0 = s_w[k];
+    t1 = t0;
+    w1 = w0;
+    if (POOL) {
+        t1 = s_tap[k + Ks];
+        w1 = s_w[k + Ks];
+    }
+}
+
+// one channel of the pooled sample: the maximum of the two samples (epipolar.py:200-202, 211-213)
+template <bool POOL>
+__device__ __forceinline__ float gen_pooled(const float *map, int ch, int c, const int4 t0, const float4 w0, const int4 t1,
+                                            const float4 w1)
+{
+    float v = gen_sample(map, ch, c, t0, w0);
+    if (POOL) v = fmaxf(v, gen_sample(map, ch, c, t1, w1));
+    return v;
+}
+
+// ... and which sample won it: the second only when strictly larger (the first on a tie, as torch.max)
+template <bool POOL>
+__device__ __forceinline__ float gen_pooled_argwin(const float *map, int ch, int c, const int4 t0, const float4 w0,
+                                                   const int4 t1, const float4 w1, bool &second)
+{
+    const float v0 = gen_sample(map, ch, c, t0, w0);
+    second = false;
+    float v = v0;
+    if (POOL) {
+        const float v1 = gen_sample(map, ch, c, t1, w1);
+        second = v1 > v0;
+        v = second ? v1 : v0;
+    }
+    return v;
+}
+
+// lanes <-> channels: dot = q . P_k' over the wave, and vv = |P_k'|^2 (summed over the wave under the cosine similarity only)
+template <bool POOL>
+__device__ __forceinline__ void gen_similarity(const GeneralParams &p, const float *m1, int lane, const float (&qv)[kGenMaxQ],
+                                               const int4 t0, const float4 w0, const int4 t1, const float4 w1, float &dot,
+                                               float &vv)
+{
+    dot = 0.f;
+    vv = 0.f;
+#pragma unroll
+    for (int i = 0; i < kGenMaxQ; ++i) {
+        const int c = lane + i * kWave;
+        if (c < p.cs) {
+            const float v = gen_pooled<POOL>(m1, p.cs, c, t0, w0, t1, w1);
+            dot = fmaf(qv[i], v, dot);
+            vv = fmaf(v, v, vv);
+        }
+    }
+    dot = wave_all_sum(dot);
+    if (p.cosine) vv = wave_all_sum(vv);
+}
+
+// lanes <-> samples: kGenKPL slots of 64 hold the K' <= K values of a pixel, and validate() admits K <= 256
+constexpr int kGenKPL = 4;
+static_assert(kGenKPL * kWave == 256, "the lanes <-> samples phases must hold validate()'s largest K");
+
+// first maximum over k' (torch.argmax) of a[s] = value of k' = s * 64 + lane: largest value, then lowest index
+__device__ __forceinline__ int gen_first_argmax(const float (&a)[kGenKPL], int Ks, int lane)
+{
+    float bestv = -__builtin_huge_valf(), bestk = 1e9f;
+#pragma unroll
+    for (int s = 0; s < kGenKPL; ++s) {
+        const int k = s * kWave + lane;
+        if (k < Ks && a[s] > bestv) {
+            bestv = a[s];
+            bestk = (float)k;
+        }
+    }
+    const float bm = wave_all_max(bestv);
+    return (int)wave_all_min((bestv == bm) ? bestk : 1e9f);
+}
+
 template <bool POOL>
 __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_fwd_general_kernel(const GeneralParams p)
 {
@@ -64,65 +196,30 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_fwd_general_kernel(
     const int H = d.H, W = d.W, K = d.K, HW = H * W;
     const int Ks = POOL ? K / 2 : K;          // similarities per pixel
     const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long long gp = (long long)blockIdx.x * kGenWaves + wave;
-    const int n = (int)(gp / HW);
-    if (n >= d.N) return;                     // wave-uniform; the kernel has no block-wide barrier
-    const int pix = (int)(gp - (long long)n * HW);
-    const int h = pix / W, w = pix - h * W;
-    float4 *s_w = reinterpret_cast<float4 *>(s_dyn + (size_t)wave * gen_wave_floats(K));   // [K] bilinear weights
-    int4 *s_tap = reinterpret_cast<int4 *>(s_w + K);                          // [K] taps
-    float *s_sim = reinterpret_cast<float *>(s_tap + K);                      // [K'] similarity, then attention
     const float neg_inf = -__builtin_huge_valf();
 
     // ---- lanes <-> samples: the epipolar segment and every sample's taps ------------------------------------------
-    const et::Segment seg = et::epipolar_segment(d, p.cam + (size_t)n * ET_CAM_STRIDE, p.xs[w], p.ys[h]);
-    for (int k = lane; k < K; k += kWave) {
-        const et::SampleSetup su = et::sample_setup(d, seg, p.steps[k]);
-        s_w[k] = make_float4(su.weight[0], su.weight[1], su.weight[2], su.weight[3]);
-        s_tap[k] = make_int4(su.tap[0], su.tap[1], su.tap[2], su.tap[3]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    GenPixel px;
+    if (!gen_pixel(p, s_dyn, gen_wave_floats(K), lane, px)) return;
+    const int n = px.n, pix = px.pix;
+    const float4 *s_w = px.s_w;
+    const int4 *s_tap = px.s_tap;
+    float *s_sim = px.s_sim;                  // [K'] similarity, then attention
 
     // ---- lanes <-> channels: similarities (epipolar.py:294-295 on the pooled samples) -----------------------------
     if (!p.sim_prior) {
         const float *qrow = p.q + ((size_t)n * HW + pix) * p.cs;
         const float *m1 = p.m_sim + (size_t)n * HW * p.cs;
         float qv[kGenMaxQ];
-#pragma unroll
-        for (int i = 0; i < kGenMaxQ; ++i) qv[i] = (lane + i * kWave < p.cs) ? qrow[lane + i * kWave] : 0.f;
-        float qq = 0.f;
-        if (p.cosine) {
-#pragma unroll
-            for (int i = 0; i < kGenMaxQ; ++i) qq = fmaf(qv[i], qv[i], qq);
-            qq = wave_all_sum(qq);
-        }
+        const float qq = gen_query(p, qrow, lane, qv);
         for (int k = 0; k < Ks; ++k) {
-            const int4 t0 = s_tap[k];
-            const float4 w0 = s_w[k];
-            int4 t1 = t0;
-            float4 w1 = w0;
-            if (POOL) {
-                t1 = s_tap[k + Ks];
-                w1 = s_w[k + Ks];
-            }
-            float dot = 0.f, vv = 0.f;
-#pragma unroll
-            for (int i = 0; i < kGenMaxQ; ++i) {
-                const int c = lane + i * kWave;
-                if (c < p.cs) {
-                    float v = gen_sample(m1, p.cs, c, t0, w0);
-                    if (POOL) v = fmaxf(v, gen_sample(m1, p.cs, c, t1, w1));
-                    dot = fmaf(qv[i], v, dot);
-                    vv = fmaf(v, v, vv);
-                }
-            }
-            dot = wave_all_sum(dot);
-            if (p.cosine) {   // epipolar.py:282-286 / :290-293: x1 . x2 / (max(|x1|, eps) max(|x2|, eps)), eps = 1e-8
-                vv = wave_all_sum(vv);
-                dot = dot / (fmaxf(sqrtf(qq), 1e-8f) * fmaxf(sqrtf(vv), 1e-8f));
-            }
+            int4 t0, t1;
+            float4 w0, w1;
+            gen_taps<POOL>(s_tap, s_w, k, Ks, t0, w0, t1, w1);
+            float dot, vv;
+            gen_similarity<POOL>(p, m1, lane, qv, t0, w0, t1, w1, dot, vv);
+            // epipolar.py:282-286 / :290-293: x1 . x2 / (max(|x1|, eps) max(|x2|, eps)), eps = 1e-8
+            if (p.cosine) dot = dot / (fmaxf(sqrtf(qq), 1e-8f) * fmaxf(sqrtf(vv), 1e-8f));
             if (lane == 0) s_sim[k] = dot;
         }
     }
@@ -131,7 +228,7 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_fwd_general_kernel(
 
     // ---- lanes <-> samples: mask, prior, soft-max, arg-max (epipolar.py:298-311, :237-241) -------------------------
     {
-        constexpr int KPL = 4;   // K' <= 256
+        constexpr int KPL = kGenKPL;
         float l[KPL], a[KPL], pr[KPL];
         float vmax = neg_inf;
 #pragma unroll
@@ -168,18 +265,7 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_fwd_general_kernel(
 #pragma unroll
             for (int s = 0; s < KPL; ++s) a[s] = (s * kWave + lane < Ks) ? l[s] : 0.f;
         }
-        // first maximum over k' (torch.argmax): largest value, then lowest index
-        float bestv = neg_inf, bestk = 1e9f;
-#pragma unroll
-        for (int s = 0; s < KPL; ++s) {
-            const int k = s * kWave + lane;
-            if (k < Ks && a[s] > bestv) {
-                bestv = a[s];
-                bestk = (float)k;
-            }
-        }
-        const float bm = wave_all_max(bestv);
-        const int besti = (int)wave_all_min((bestv == bm) ? bestk : 1e9f);
+        const int besti = gen_first_argmax(a, Ks, lane);
 #pragma unroll
         for (int s = 0; s < KPL; ++s) {
             const int k = s * kWave + lane;
@@ -191,7 +277,7 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_fwd_general_kernel(
         }
         if (p.corr && lane == 0 && besti < Ks) {
             // the location of sample `besti` of the UNPOOLED list: sample_locs[idx], idx < K' (epipolar.py:239)
-            const et::SampleSetup su = et::sample_setup(d, seg, p.steps[besti]);
+            const et::SampleSetup su = et::sample_setup(d, px.seg, p.steps[besti]);
             float *o = p.corr + ((size_t)n * HW + pix) * 2;
             o[0] = et::de_normalize(d, su.nx, W);
             o[1] = et::de_normalize(d, su.ny, H);
@@ -209,22 +295,13 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_fwd_general_kernel(
             for (int k = 0; k < Ks; ++k) {
                 const float ak = s_sim[k];
                 if (p.attn_max && ak == 0.f) continue;      // wave-uniform (the one-hot weights of ATTENTION max)
-                const int4 t0 = s_tap[k];
-                const float4 w0 = s_w[k];
-                int4 t1 = t0;
-                float4 w1 = w0;
-                if (POOL) {
-                    t1 = s_tap[k + Ks];
-                    w1 = s_w[k + Ks];
-                }
+                int4 t0, t1;
+                float4 w0, w1;
+                gen_taps<POOL>(s_tap, s_w, k, Ks, t0, w0, t1, w1);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int c = c0 + lane + i * kWave;
-                    if (c < p.cv) {
-                        float v = gen_sample(m2, p.cv, c, t0, w0);
-                        if (POOL) v = fmaxf(v, gen_sample(m2, p.cv, c, t1, w1));
-                        acc[i] = fmaf(ak, v, acc[i]);
-                    }
+                    if (c < p.cv) acc[i] = fmaf(ak, gen_pooled<POOL>(m2, p.cv, c, t0, w0, t1, w1), acc[i]);
                 }
             }
 #pragma unroll
@@ -284,74 +361,34 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_bwd_general_kernel(
     const int H = d.H, W = d.W, K = d.K, HW = H * W;
     const int Ks = POOL ? K / 2 : K;
     const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long long gp = (long long)blockIdx.x * kGenWaves + wave;
-    const int n = (int)(gp / HW);
-    if (n >= d.N) return;
-    const int pix = (int)(gp - (long long)n * HW);
-    const int h = pix / W, w = pix - h * W;
-    float4 *s_w = reinterpret_cast<float4 *>(s_dyn + (size_t)wave * gen_bwd_wave_floats(K));
-    int4 *s_tap = reinterpret_cast<int4 *>(s_w + K);
-    float *s_sim = reinterpret_cast<float *>(s_tap + K);   // [K'] q . P, then alpha
-    float *s_a = s_sim + K;                                 // [K'] d a, then a
-    float *s_b = s_a + K;                                   // [K'] |P|^2 (cosine), then beta
     const float neg_inf = -__builtin_huge_valf();
     const float kEps = 1e-8f;
 
-    const et::Segment seg = et::epipolar_segment(d, p.cam + (size_t)n * ET_CAM_STRIDE, p.xs[w], p.ys[h]);
-    for (int k = lane; k < K; k += kWave) {
-        const et::SampleSetup su = et::sample_setup(d, seg, p.steps[k]);
-        s_w[k] = make_float4(su.weight[0], su.weight[1], su.weight[2], su.weight[3]);
-        s_tap[k] = make_int4(su.tap[0], su.tap[1], su.tap[2], su.tap[3]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    GenPixel px;
+    if (!gen_pixel(p, s_dyn, gen_bwd_wave_floats(K), lane, px)) return;
+    const int n = px.n, pix = px.pix;
+    const float4 *s_w = px.s_w;
+    const int4 *s_tap = px.s_tap;
+    float *s_sim = px.s_sim;                                // [K'] q . P, then alpha
+    float *s_a = s_sim + K;                                 // [K'] d a, then a
+    float *s_b = s_a + K;                                   // [K'] |P|^2 (cosine), then beta
 
     const float *qrow = p.q + ((size_t)n * HW + pix) * p.cs;
     const float *grow = bp.gout + ((size_t)n * HW + pix) * p.cv;
     const float *m1 = p.m_sim + (size_t)n * HW * p.cs;
     const float *m2 = p.m_val + (size_t)n * HW * p.cv;
     float qv[kGenMaxQ];
-#pragma unroll
-    for (int i = 0; i < kGenMaxQ; ++i) qv[i] = (lane + i * kWave < p.cs) ? qrow[lane + i * kWave] : 0.f;
-    float qq = 0.f;
-    if (p.cosine) {
-#pragma unroll
-        for (int i = 0; i < kGenMaxQ; ++i) qq = fmaf(qv[i], qv[i], qq);
-        qq = wave_all_sum(qq);
-    }
+    const float qq = gen_query(p, qrow, lane, qv);
 
     // ---- lanes <-> channels: q . P_k' (and |P_k'|^2)  and  d a_k' = g . V_k' ------------------------------------------
     for (int k = 0; k < Ks; ++k) {
-        const int4 t0 = s_tap[k];
-        const float4 w0 = s_w[k];
-        int4 t1 = t0;
-        float4 w1 = w0;
-        if (POOL) {
-            t1 = s_tap[k + Ks];
-            w1 = s_w[k + Ks];
-        }
+        int4 t0, t1;
+        float4 w0, w1;
+        gen_taps<POOL>(s_tap, s_w, k, Ks, t0, w0, t1, w1);
         float dot = 0.f, vv = 0.f, da = 0.f;
-        if (!p.sim_prior) {
-#pragma unroll
-            for (int i = 0; i < kGenMaxQ; ++i) {
-                const int c = lane + i * kWave;
-                if (c < p.cs) {
-                    float v = gen_sample(m1, p.cs, c, t0, w0);
-                    if (POOL) v = fmaxf(v, gen_sample(m1, p.cs, c, t1, w1));
-                    dot = fmaf(qv[i], v, dot);
-                    vv = fmaf(v, v, vv);
-                }
-            }
-            dot = wave_all_sum(dot);
-            if (p.cosine) vv = wave_all_sum(vv);
-        }
+        if (!p.sim_prior) gen_similarity<POOL>(p, m1, lane, qv, t0, w0, t1, w1, dot, vv);
         if (!p.attn_max) {
-            for (int c = lane; c < p.cv; c += kWave) {
-                float v = gen_sample(m2, p.cv, c, t0, w0);
-                if (POOL) v = fmaxf(v, gen_sample(m2, p.cv, c, t1, w1));
-                da = fmaf(grow[c], v, da);
-            }
+            for (int c = lane; c < p.cv; c += kWave) da = fmaf(grow[c], gen_pooled<POOL>(m2, p.cv, c, t0, w0, t1, w1), da);
             da = wave_all_sum(da);
         }
         if (lane == 0) {
@@ -366,7 +403,7 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_bwd_general_kernel(
     // ---- lanes <-> samples: a (recomputed), d prior, and the coefficients alpha / beta / gamma of the maps' gradients ----
     float gamma = 0.f;
     {
-        constexpr int KPL = 4;
+        constexpr int KPL = kGenKPL;
         const float nq = fmaxf(sqrtf(qq), kEps);
         float sim[KPL], da[KPL], pr[KPL], np_[KPL], aout[KPL], alpha[KPL], beta[KPL], dprior[KPL];
 #pragma unroll
@@ -394,17 +431,7 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_bwd_general_kernel(
         };
         if (p.attn_max) {
             // first maximum over k' (torch.argmax): a one-hot weight, nothing flows from `out` through the similarity
-            float bestv = neg_inf, bestk = 1e9f;
-#pragma unroll
-            for (int s = 0; s < KPL; ++s) {
-                const int k = s * kWave + lane;
-                if (k < Ks && sim[s] > bestv) {
-                    bestv = sim[s];
-                    bestk = (float)k;
-                }
-            }
-            const float bm = wave_all_max(bestv);
-            const int besti = (int)wave_all_min((bestv == bm) ? bestk : 1e9f);
+            const int besti = gen_first_argmax(sim, Ks, lane);
 #pragma unroll
             for (int s = 0; s < KPL; ++s) aout[s] = (s * kWave + lane == besti) ? 1.f : 0.f;
             if (bp.gattn) {
@@ -500,27 +527,16 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_bwd_general_kernel(
         float *g2 = bp.gval ? bp.gval + (size_t)n * HW * p.cv : nullptr;
         for (int k = 0; k < Ks; ++k) {
             const float al = s_sim[k], be = s_b[k], ak = s_a[k];
-            const int4 t0 = s_tap[k];
-            const float4 w0 = s_w[k];
-            int4 t1 = t0;
-            float4 w1 = w0;
-            if (POOL) {
-                t1 = s_tap[k + Ks];
-                w1 = s_w[k + Ks];
-            }
+            int4 t0, t1;
+            float4 w0, w1;
+            gen_taps<POOL>(s_tap, s_w, k, Ks, t0, w0, t1, w1);
             if (al != 0.f || be != 0.f) {    // wave-uniform
 #pragma unroll
                 for (int i = 0; i < kGenMaxQ; ++i) {
                     const int c = lane + i * kWave;
                     if (c < p.cs) {
-                        const float v0 = gen_sample(m1, p.cs, c, t0, w0);
-                        bool second = false;
-                        float v = v0;
-                        if (POOL) {
-                            const float v1 = gen_sample(m1, p.cs, c, t1, w1);
-                            second = v1 > v0;
-                            v = second ? v1 : v0;
-                        }
+                        bool second;
+                        const float v = gen_pooled_argwin<POOL>(m1, p.cs, c, t0, w0, t1, w1, second);
                         dq[i] = fmaf(al, v, dq[i]);
                         if (g1) gen_scatter(g1, p.cs, c, second ? t1 : t0, second ? w1 : w0, al * qv[i] - be * v);
                     }
@@ -528,8 +544,8 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_bwd_general_kernel(
             }
             if (g2 && ak != 0.f) {
                 for (int c = lane; c < p.cv; c += kWave) {
-                    bool second = false;
-                    if (POOL) second = gen_sample(m2, p.cv, c, t1, w1) > gen_sample(m2, p.cv, c, t0, w0);
+                    bool second;   // only the winner is needed here: without POOL the unused sample is dead code, no load
+                    gen_pooled_argwin<POOL>(m2, p.cv, c, t0, w0, t1, w1, second);
                     gen_scatter(g2, p.cv, c, second ? t1 : t0, second ? w1 : w0, ak * grow[c]);
                 }
             }
@@ -550,6 +566,55 @@ int check_sim_prior(const char *who, int flags, bool has_prior)
         return fail("%s: SIM_PRIOR excludes PRIOR_MUL / COSINE (flags=%d)", who, flags);
     return 0;
 }
+
+// The argument checks of both entry points, then the inputs of the parameter block (out / attn / corr are the caller's) and
+// the grid.  `written` is the output every call writes: the forward's out, the backward's grad_q.  `backward`: grad_out is
+// required too, and a grad_prior needs a prior.
+int general_params(const char *who, bool backward, const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                   const float *cam, const float *q, const float *map_sim, const float *map_val, const float *prior, int c_sim,
+                   int c_val, int flags, const float *written, const float *grad_out, const float *grad_prior, GeneralParams &p,
+                   unsigned &blocks)
+{
+    if (!desc) return fail("%s: desc is NULL", who);
+    EtLayerDesc chk = *desc;
+    chk.C = 4;                                   // (the channel counts of these entry points are c_sim / c_val)
+    if (int e = validate(&chk)) return e;        // K <= 256, so K' fits the kernels' kGenKPL lane slots
+    if (!xs || !ys || !steps || !cam || !q || !map_sim || !map_val || !written || (backward && !grad_out))
+        return fail("%s: NULL pointer", who);
+    if (c_sim <= 0 || c_sim > kGenMaxQ * kWave) return fail("%s: c_sim=%d outside [1, %d]", who, c_sim, kGenMaxQ * kWave);
+    if (c_val <= 0 || c_val > 4096) return fail("%s: c_val=%d outside [1, 4096]", who, c_val);
+    if (flags & ~(ET_GENERAL_POOLING | ET_GENERAL_PRIOR_MUL | ET_GENERAL_COSINE | ET_GENERAL_ATTENTION_MAX | ET_GENERAL_SIM_PRIOR))
+        return fail("%s: unknown flag bits %d", who, flags);
+    if ((flags & ET_GENERAL_ATTENTION_MAX) && prior && !(flags & ET_GENERAL_SIM_PRIOR))
+        return fail("%s: ATTENTION max takes no prior", who);
+    if (int e = check_sim_prior(who, flags, prior != nullptr)) return e;
+    if ((flags & ET_GENERAL_POOLING) && (desc->K & 1)) return fail("%s: POOLING needs an even K (K=%d)", who, desc->K);
+    if ((flags & ET_GENERAL_PRIOR_MUL) && !prior) return fail("%s: PRIOR_MUL without a prior", who);
+    if (backward && grad_prior && !prior) return fail("%s: grad_prior without a prior", who);
+    const long long hw = (long long)desc->H * desc->W;
+    if (hw * (c_sim > c_val ? c_sim : c_val) * 4 >= (1LL << 31)) return fail("one feature map must stay below 2 GiB");
+    p.d = *desc;
+    p.xs = xs; p.ys = ys; p.steps = steps; p.cam = cam;
+    p.q = q; p.m_sim = map_sim; p.m_val = map_val; p.prior = prior;
+    p.cs = c_sim; p.cv = c_val; p.prior_mul = (flags & ET_GENERAL_PRIOR_MUL) ? 1 : 0;
+    p.attn_max = (flags & ET_GENERAL_ATTENTION_MAX) ? 1 : 0;
+    p.cosine = (flags & (ET_GENERAL_COSINE | ET_GENERAL_ATTENTION_MAX)) ? 1 : 0;   // (ATTENTION max is always cosine, epipolar.py:282)
+    p.sim_prior = (flags & ET_GENERAL_SIM_PRIOR) ? 1 : 0;
+    const long long nblocks = (hw * desc->N + kGenWaves - 1) / kGenWaves;
+    if (nblocks > 0x7fffffffLL) return fail("grid too large");
+    blocks = (unsigned)nblocks;
+    return 0;
+}
+
+// one wave per reference pixel; the POOLING switch is a template parameter of the kernels
+template <class P>
+int launch_general(const char *who, bool pool, void (*pooled)(P), void (*plain)(P), unsigned blocks, size_t lds, void *stream,
+                   const P &p)
+{
+    void (*kernel)(P) = pool ? pooled : plain;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kWave * kGenWaves), lds, (hipStream_t)stream, p);
+    return check_launch(who);
+}
 }  // namespace
 
 extern "C" {
@@ -559,40 +624,15 @@ int et_epipolar_forward_general(const EtLayerDesc *desc, const float *xs, const 
                                 const float *prior, int c_sim, int c_val, int flags, float *out, float *attn,
                                 float *corr_pos, void *stream)
 {
-    if (!desc) return fail("et_epipolar_forward_general: desc is NULL");
-    EtLayerDesc chk = *desc;
-    chk.C = 4;                                   // (the channel counts of this entry point are c_sim / c_val)
-    if (int e = validate(&chk)) return e;
-    if (!xs || !ys || !steps || !cam || !q || !map_sim || !map_val || !out)
-        return fail("et_epipolar_forward_general: NULL pointer");
-    if (c_sim <= 0 || c_sim > kGenMaxQ * kWave) return fail("et_epipolar_forward_general: c_sim=%d outside [1, %d]", c_sim, kGenMaxQ * kWave);
-    if (c_val <= 0 || c_val > 4096) return fail("et_epipolar_forward_general: c_val=%d outside [1, 4096]", c_val);
-    if (flags & ~(ET_GENERAL_POOLING | ET_GENERAL_PRIOR_MUL | ET_GENERAL_COSINE | ET_GENERAL_ATTENTION_MAX | ET_GENERAL_SIM_PRIOR))
-        return fail("et_epipolar_forward_general: unknown flag bits %d", flags);
-    if ((flags & ET_GENERAL_ATTENTION_MAX) && prior && !(flags & ET_GENERAL_SIM_PRIOR))
-        return fail("et_epipolar_forward_general: ATTENTION max takes no prior");
-    if (int e = check_sim_prior("et_epipolar_forward_general", flags, prior != nullptr)) return e;
-    const bool pool = flags & ET_GENERAL_POOLING;
-    if (pool && (desc->K & 1)) return fail("et_epipolar_forward_general: POOLING needs an even K (K=%d)", desc->K);
-    if ((flags & ET_GENERAL_PRIOR_MUL) && !prior) return fail("et_epipolar_forward_general: PRIOR_MUL without a prior");
-    const long long hw = (long long)desc->H * desc->W;
-    if (hw * (c_sim > c_val ? c_sim : c_val) * 4 >= (1LL << 31)) return fail("one feature map must stay below 2 GiB");
+    const char *who = "et_epipolar_forward_general";
     GeneralParams p;
-    p.d = *desc;
-    p.xs = xs; p.ys = ys; p.steps = steps; p.cam = cam;
-    p.q = q; p.m_sim = map_sim; p.m_val = map_val; p.prior = prior;
+    unsigned blocks;
+    if (int e = general_params(who, false, desc, xs, ys, steps, cam, q, map_sim, map_val, prior, c_sim, c_val, flags, out, nullptr,
+                               nullptr, p, blocks))
+        return e;
     p.out = out; p.attn = attn; p.corr = corr_pos;
-    p.cs = c_sim; p.cv = c_val; p.prior_mul = (flags & ET_GENERAL_PRIOR_MUL) ? 1 : 0;
-    p.attn_max = (flags & ET_GENERAL_ATTENTION_MAX) ? 1 : 0;
-    p.cosine = (flags & (ET_GENERAL_COSINE | ET_GENERAL_ATTENTION_MAX)) ? 1 : 0;   // (ATTENTION max is always cosine, epipolar.py:282)
-    p.sim_prior = (flags & ET_GENERAL_SIM_PRIOR) ? 1 : 0;
-    const long long blocks = (hw * desc->N + kGenWaves - 1) / kGenWaves;
-    if (blocks > 0x7fffffffLL) return fail("grid too large");
-    const size_t lds = gen_lds_bytes(desc->K);
-    hipStream_t st = (hipStream_t)stream;
-    if (pool) hipLaunchKernelGGL(epipolar_fwd_general_kernel<true>, dim3((unsigned)blocks), dim3(kWave * kGenWaves), lds, st, p);
-    else hipLaunchKernelGGL(epipolar_fwd_general_kernel<false>, dim3((unsigned)blocks), dim3(kWave * kGenWaves), lds, st, p);
-    return check_launch("et_epipolar_forward_general");
+    return launch_general(who, flags & ET_GENERAL_POOLING, epipolar_fwd_general_kernel<true>, epipolar_fwd_general_kernel<false>,
+                          blocks, gen_lds_bytes(desc->K), stream, p);
 }
 
 int et_epipolar_backward_general(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
@@ -610,43 +650,17 @@ int et_epipolar_backward_general_ga(const EtLayerDesc *desc, const float *xs, co
                                     int flags, float *grad_q, float *grad_map_sim, float *grad_map_val, float *grad_prior,
                                     void *stream)
 {
-    if (!desc) return fail("et_epipolar_backward_general: desc is NULL");
-    EtLayerDesc chk = *desc;
-    chk.C = 4;
-    if (int e = validate(&chk)) return e;
-    if (!xs || !ys || !steps || !cam || !q || !map_sim || !map_val || !grad_out || !grad_q)
-        return fail("et_epipolar_backward_general: NULL pointer");
-    if (c_sim <= 0 || c_sim > kGenMaxQ * kWave) return fail("et_epipolar_backward_general: c_sim=%d outside [1, %d]", c_sim, kGenMaxQ * kWave);
-    if (c_val <= 0 || c_val > 4096) return fail("et_epipolar_backward_general: c_val=%d outside [1, 4096]", c_val);
-    if (flags & ~(ET_GENERAL_POOLING | ET_GENERAL_PRIOR_MUL | ET_GENERAL_COSINE | ET_GENERAL_ATTENTION_MAX | ET_GENERAL_SIM_PRIOR))
-        return fail("et_epipolar_backward_general: unknown flag bits %d", flags);
-    if ((flags & ET_GENERAL_ATTENTION_MAX) && prior && !(flags & ET_GENERAL_SIM_PRIOR))
-        return fail("et_epipolar_backward_general: ATTENTION max takes no prior");
-    if ((flags & ET_GENERAL_PRIOR_MUL) && !prior) return fail("et_epipolar_backward_general: PRIOR_MUL without a prior");
-    if (int e = check_sim_prior("et_epipolar_backward_general", flags, prior != nullptr)) return e;
-    if (grad_prior && !prior) return fail("et_epipolar_backward_general: grad_prior without a prior");
-    if (desc->K > 256 * ((flags & ET_GENERAL_POOLING) ? 2 : 1)) return fail("et_epipolar_backward_general: K' = %d > 256", desc->K);
-    const bool pool = flags & ET_GENERAL_POOLING;
-    if (pool && (desc->K & 1)) return fail("et_epipolar_backward_general: POOLING needs an even K (K=%d)", desc->K);
-    const long long hw = (long long)desc->H * desc->W;
-    if (hw * (c_sim > c_val ? c_sim : c_val) * 4 >= (1LL << 31)) return fail("one feature map must stay below 2 GiB");
+    const char *who = "et_epipolar_backward_general";
     GeneralBwdParams bp;
-    bp.f.d = *desc;
-    bp.f.xs = xs; bp.f.ys = ys; bp.f.steps = steps; bp.f.cam = cam;
-    bp.f.q = q; bp.f.m_sim = map_sim; bp.f.m_val = map_val; bp.f.prior = prior;
+    unsigned blocks;
+    if (int e = general_params(who, true, desc, xs, ys, steps, cam, q, map_sim, map_val, prior, c_sim, c_val, flags, grad_q, grad_out,
+                               grad_prior, bp.f, blocks))
+        return e;
     bp.f.out = nullptr; bp.f.attn = nullptr; bp.f.corr = nullptr;
-    bp.f.cs = c_sim; bp.f.cv = c_val; bp.f.prior_mul = (flags & ET_GENERAL_PRIOR_MUL) ? 1 : 0;
-    bp.f.attn_max = (flags & ET_GENERAL_ATTENTION_MAX) ? 1 : 0;
-    bp.f.cosine = (flags & (ET_GENERAL_COSINE | ET_GENERAL_ATTENTION_MAX)) ? 1 : 0;
-    bp.f.sim_prior = (flags & ET_GENERAL_SIM_PRIOR) ? 1 : 0;
     bp.gout = grad_out; bp.gattn = grad_attn; bp.gq = grad_q; bp.gsim = grad_map_sim; bp.gval = grad_map_val; bp.gprior = grad_prior;
-    const long long blocks = (hw * desc->N + kGenWaves - 1) / kGenWaves;
-    if (blocks > 0x7fffffffLL) return fail("grid too large");
     const size_t lds = (size_t)kGenWaves * gen_bwd_wave_floats(desc->K) * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
-    if (pool) hipLaunchKernelGGL(epipolar_bwd_general_kernel<true>, dim3((unsigned)blocks), dim3(kWave * kGenWaves), lds, st, bp);
-    else hipLaunchKernelGGL(epipolar_bwd_general_kernel<false>, dim3((unsigned)blocks), dim3(kWave * kGenWaves), lds, st, bp);
-    return check_launch("et_epipolar_backward_general");
+    return launch_general(who, flags & ET_GENERAL_POOLING, epipolar_bwd_general_kernel<true>, epipolar_bwd_general_kernel<false>,
+                          blocks, lds, stream, bp);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// Part of epipolar_kernels.hip (one translation unit, one anonymous namespace): the backward kernels (atomic scatter, and emit / scan / bucket / gather).
-// Included from epipolar_kernels.hip after the shared device helpers; not a stand-alone header.
+// Part of et_backward.hip (inside its anonymous namespace, after et_common.h / kernels_sample_table.inc /
+// kernels_pixel_phases.inc): the backward kernels (atomic scatter, and emit / scan / bucket / gather).  Not a stand-alone header.
 // ----------------------------------------------------------------------------
 // backward
 // ----------------------------------------------------------------------------
@@ -103,61 +103,13 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_kernel(con
                         }
                     }
                 }
-                const float u1 = reduce8<FAST>(p1, lane);
-                const float u2 = reduce8<FAST>(p2, lane);
-                const bool masked = (u1 == 0.f);
-                float sv = masked ? -1e10f : u1;
-                sv = d.softmax_enabled ? sv * d.softmax_scale : sv / (float)K;
-                const int srcl = lane_of_sample<8>(lane & 7);
-                const float mine_l = __shfl(sv, srcl);
-                const float mine_d = __shfl(u2, srcl);
-                const int mine_m = __shfl((int)masked, srcl);
-                if ((lane >> 3) == (kb >> 3)) {
-                    v_logit[s] = mine_l;
-                    v_da[s] = mine_d;
-                    v_masked[s] = mine_m != 0;
-                }
+                keep_batch<KPL, FAST>(d, K, lane, s, kb, p1, p2, v_logit, v_da, v_masked);
             }
         }
 
         // ---------------- soft-max gradient, lanes <-> samples -----------------
-        if (p.gattn) {  // block-uniform: d loss / d attn_k reaches a_k beside e_k = g . S_k (include/epipolar_amd.h)
-            const float *ga = p.gattn + (size_t)n * K * HW + pix;
-#pragma unroll
-            for (int s = 0; s < KPL; ++s)
-                if (s * kWave + lane < K) v_da[s] += ga[(size_t)(s * kWave + lane) * HW];
-        }
         float v_a[KPL], v_ds[KPL];
-        if (d.softmax_enabled) {
-            float mx = neg_inf;
-#pragma unroll
-            for (int s = 0; s < KPL; ++s) mx = fmaxf(mx, (s * kWave + lane < K) ? v_logit[s] : neg_inf);
-            mx = wave_max(mx);
-            float lsum = 0.f;
-#pragma unroll
-            for (int s = 0; s < KPL; ++s) {
-                v_a[s] = (s * kWave + lane < K) ? expf(v_logit[s] - mx) : 0.f;
-                lsum += v_a[s];
-            }
-            const float denom = wave_sum(lsum);
-            float dsum = 0.f;
-#pragma unroll
-            for (int s = 0; s < KPL; ++s) {
-                v_a[s] = v_a[s] / denom;
-                dsum = fmaf(v_a[s], v_da[s], dsum);
-            }
-            const float dot = wave_sum(dsum);
-#pragma unroll
-            for (int s = 0; s < KPL; ++s)
-                v_ds[s] = v_masked[s] ? 0.f : d.softmax_scale * v_a[s] * (v_da[s] - dot);
-        } else {
-#pragma unroll
-            for (int s = 0; s < KPL; ++s) {
-                const bool in = s * kWave + lane < K;
-                v_a[s] = in ? v_logit[s] : 0.f;  // already sim / K
-                v_ds[s] = (in && !v_masked[s]) ? v_da[s] / (float)K : 0.f;
-            }
-        }
+        softmax_grad<KPL>(p, n, pix, lane, v_logit, v_da, v_masked, v_a, v_ds);
 
         // ---------------- pass B: d(feat_ref) and scatter of d(feat_src) --------
         float d1[CPD], G[4][CPD];
@@ -327,61 +279,14 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_emit_kerne
                         }
                     }
                 }
-                const float u1 = reduce8<FAST>(p1, lane);
-                const float u2 = reduce8<FAST>(p2, lane);
-                const bool masked = (u1 == 0.f);
-                float sv = masked ? -1e10f : u1;
-                sv = d.softmax_enabled ? sv * d.softmax_scale : sv / (float)K;
-                const int srcl = lane_of_sample<8>(lane & 7);
-                const float mine_l = __shfl(sv, srcl);
-                const float mine_d = __shfl(u2, srcl);
-                const int mine_m = __shfl((int)masked, srcl);
-                if ((lane >> 3) == (kb >> 3)) {
-                    v_logit[s] = mine_l;
-                    v_da[s] = mine_d;
-                    v_masked[s] = mine_m != 0;
-                }
+                keep_batch<KPL, FAST>(d, K, lane, s, kb, p1, p2, v_logit, v_da, v_masked);
             }
         }
 
         // ---------------- soft-max gradient, lanes <-> samples -----------------------
-        if (p.gattn) {  // block-uniform: d loss / d attn_k reaches a_k beside e_k = g . S_k (include/epipolar_amd.h)
-            const float *ga = p.gattn + (size_t)n * K * HW + pix;
-#pragma unroll
-            for (int s = 0; s < KPL; ++s)
-                if (s * kWave + lane < K) v_da[s] += ga[(size_t)(s * kWave + lane) * HW];
-        }
         float v_a[KPL], v_ds[KPL];
-        if (d.softmax_enabled) {
-            float mx = neg_inf;
-#pragma unroll
-            for (int s = 0; s < KPL; ++s) mx = fmaxf(mx, (s * kWave + lane < K) ? v_logit[s] : neg_inf);
-            mx = wave_max(mx);
-            float lsum = 0.f;
-#pragma unroll
-            for (int s = 0; s < KPL; ++s) {
-                v_a[s] = (s * kWave + lane < K) ? expf(v_logit[s] - mx) : 0.f;
-                lsum += v_a[s];
-            }
-            const float denom = wave_sum(lsum);
-            float dsum = 0.f;
-#pragma unroll
-            for (int s = 0; s < KPL; ++s) {
-                v_a[s] = v_a[s] / denom;
-                dsum = fmaf(v_a[s], v_da[s], dsum);
-            }
-            const float dot = wave_sum(dsum);
-#pragma unroll
-            for (int s = 0; s < KPL; ++s)
-                v_ds[s] = v_masked[s] ? 0.f : d.softmax_scale * v_a[s] * (v_da[s] - dot);
-        } else {
-#pragma unroll
-            for (int s = 0; s < KPL; ++s) {
-                const bool in = s * kWave + lane < K;
-                v_a[s] = in ? v_logit[s] : 0.f;
-                v_ds[s] = (in && !v_masked[s]) ? v_da[s] / (float)K : 0.f;
-            }
-        }
+        softmax_grad<KPL>(p, n, pix, lane, v_logit, v_da, v_masked, v_a, v_ds);
+
         // ---------------- pass B: d(feat_ref) and the coefficient entries ----------------
         float4 d1[CPL];
 #pragma unroll

@@ -1,5 +1,5 @@
-// Part of et_forward.hip (inside its anonymous namespace, after et_common.h / kernels_sample_table.inc): the fused
-// forward kernels.  Not a stand-alone header.
+// Part of et_forward.hip (inside its anonymous namespace, after et_common.h / kernels_sample_table.inc /
+// kernels_pixel_phases.inc): the fused forward kernels.  Not a stand-alone header.
 // ----------------------------------------------------------------------------
 // forward: fused epipolar sample + dot + masked softmax + weighted sum
 // ----------------------------------------------------------------------------
@@ -85,23 +85,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_kern
 #pragma unroll
             for (int r = 0; r < 4; ++r) R[r][c] = f4_zero();
         }
-        if (p.res_base) {
-            // additive term of the residual fusion, while the reference row is still in registers
-            float4 *b4 = reinterpret_cast<float4 *>(p.res_base + ((size_t)n * HW + pix) * C);
-            const float4 *bias4 = reinterpret_cast<const float4 *>(p.res_bias);
-#pragma unroll
-            for (int c = 0; c < CPL; ++c) {
-                const int v = lane + c * kWave;
-                if (v < nvec) {
-                    float4 r = f1[c];
-                    if (bias4) {
-                        const float4 bb = bias4[v];
-                        r = make_float4(r.x + bb.x, r.y + bb.y, r.z + bb.z, r.w + bb.w);
-                    }
-                    b4[v] = r;
-                }
-            }
-        }
+        if (p.res_base) write_res_base<CPL, kWave>(p, (size_t)n * HW + pix, lane, nvec, f1);
         float m_run = neg_inf;
 
 #pragma unroll
@@ -193,26 +177,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_kern
 #pragma unroll
             for (int s = 0; s < KPL; ++s) a[s] = v_sim[s];
         }
-        // first maximum over k (torch.argmax), value then lowest index
-        float bestv = neg_inf;
-        int besti = 0x7fffffff;
-#pragma unroll
-        for (int s = 0; s < KPL; ++s) {
-            const int k = s * kWave + lane;
-            if (k < K && (a[s] > bestv)) {
-                bestv = a[s];
-                besti = k;
-            }
-        }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            const float ov = __shfl_xor(bestv, m);
-            const int oi = __shfl_xor(besti, m);
-            if (ov > bestv || (ov == bestv && oi < besti)) {
-                bestv = ov;
-                besti = oi;
-            }
-        }
+        const int besti = first_argmax<KPL>(a, K, lane);
         if (p.corr) {
             float bx = 0.f, by = 0.f;
 #pragma unroll
@@ -247,24 +212,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_kern
         }
     }
 
-    if (p.attn) {
-        __syncthreads();
-        // (N,K,H,W): for a fixed k the 16 pixels of this block are contiguous
-        const int npix = min(kPixPerBlock, HW - pix_base);
-        float *dst = p.attn + (size_t)n * K * HW + pix_base;
-        if (npix == kPixPerBlock && (HW & 3) == 0) {
-            for (int t = threadIdx.x; t < K * 4; t += blockDim.x) {
-                const int k = t >> 2, q = t & 3;
-                const float4 v = *reinterpret_cast<const float4 *>(&s_attn[k * kPixPerBlock + q * 4]);
-                *reinterpret_cast<float4 *>(dst + (size_t)k * HW + q * 4) = v;
-            }
-        } else {
-            for (int t = threadIdx.x; t < K * kPixPerBlock; t += blockDim.x) {
-                const int k = t / kPixPerBlock, i = t % kPixPerBlock;
-                if (i < npix) dst[(size_t)k * HW + i] = s_attn[k * kPixPerBlock + i];
-            }
-        }
-    }
+    if (p.attn) store_attn_tile(p, s_attn, n, pix_base);
 }
 
 // ----------------------------------------------------------------------------
@@ -356,19 +304,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_mult
 #pragma unroll
             for (int r = 0; r < 4; ++r) R[r][c] = f4_zero();
         }
-        if (p.res_base && mylive) {
-            float4 *b4 = reinterpret_cast<float4 *>(p.res_base + ((size_t)n * HW + mypix) * C);
-            const float4 *bias4 = reinterpret_cast<const float4 *>(p.res_bias);
-#pragma unroll
-            for (int c = 0; c < CQ; ++c) {
-                float4 r = f1[c];
-                if (bias4) {
-                    const float4 bb = bias4[c * LPP + li];
-                    r = make_float4(r.x + bb.x, r.y + bb.y, r.z + bb.z, r.w + bb.w);
-                }
-                b4[c * LPP + li] = r;
-            }
-        }
+        if (p.res_base && mylive) write_res_base<CQ, LPP>(p, (size_t)n * HW + mypix, li, LPP * CQ, f1);
         float m_run = neg_inf;
         const int rec0 = g * KP;
 
@@ -473,25 +409,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_mult
 #pragma unroll
                 for (int s = 0; s < KPL; ++s) a[s] = (s * kWave + lane < K) ? s_wt[gg * KP + s * kWave + lane].x : 0.f;
             }
-            float bestv = neg_inf;
-            int besti = 0x7fffffff;
-#pragma unroll
-            for (int s = 0; s < KPL; ++s) {
-                const int k = s * kWave + lane;
-                if (k < K && (a[s] > bestv)) {
-                    bestv = a[s];
-                    besti = k;
-                }
-            }
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) {
-                const float ov = __shfl_xor(bestv, m);
-                const int oi = __shfl_xor(besti, m);
-                if (ov > bestv || (ov == bestv && oi < besti)) {
-                    bestv = ov;
-                    besti = oi;
-                }
-            }
+            const int besti = first_argmax<KPL>(a, K, lane);
             if (p.corr && lane == 0) {
                 const float4 sg = s_seg[gg];
                 et::Segment seg;
@@ -518,22 +436,6 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_mult
         __builtin_amdgcn_wave_barrier();
     }
 
-    if (p.attn) {
-        __syncthreads();
-        const int npix = min(kPixPerBlock, HW - pix_base);
-        float *dst = p.attn + (size_t)n * K * HW + pix_base;
-        if (npix == kPixPerBlock && (HW & 3) == 0) {
-            for (int t = threadIdx.x; t < K * 4; t += blockDim.x) {
-                const int k = t >> 2, q = t & 3;
-                const float4 v = *reinterpret_cast<const float4 *>(&s_attn[k * kPixPerBlock + q * 4]);
-                *reinterpret_cast<float4 *>(dst + (size_t)k * HW + q * 4) = v;
-            }
-        } else {
-            for (int t = threadIdx.x; t < K * kPixPerBlock; t += blockDim.x) {
-                const int k = t / kPixPerBlock, i = t % kPixPerBlock;
-                if (i < npix) dst[(size_t)k * HW + i] = s_attn[k * kPixPerBlock + i];
-            }
-        }
-    }
+    if (p.attn) store_attn_tile(p, s_attn, n, pix_base);
 }
 
