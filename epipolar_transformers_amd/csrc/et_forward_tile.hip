@@ -238,6 +238,9 @@ int et_epipolar_forward_fused(const EtLayerDesc *desc, const float *xs, const fl
     wp.packed_w = reinterpret_cast<const unsigned *>(packed_w);
     wp.bias = bias;
     wp.x = x;
+#ifdef ET_WS_PROFILE
+    wp.prof = g_ws_prof;
+#endif
     if (int e = launch_fwd_tile_ws<true>(desc, wp, dev, st)) return e;
     if (int e = check_launch("et_epipolar_forward_fused(ws)")) return e;
     // the tiles it left over: `out` rows one block per tile (K <= 64: one sample per lane), then their x rows

@@ -68,6 +68,8 @@
 // for every tile; the whole-map table would be 2 x 20 KB there and the block is at the LDS limit).  On small maps the second
 // returns what the first returns bit for bit (tests/test_gpu_band.py) and is 10 % slower.
 
+#include "et_lds_layout.h"     // where the fp16 MFMA operands sit in LDS; G1's lane trade
+
 constexpr int kWsMatrixWaves = 4;
 constexpr int kWsSlots = 3;  // ring of set-up records (pixels, segments, row list, U)
 
@@ -99,7 +101,11 @@ struct TileWsParams {
 // are 34 dwords: lanes 16 apart collided, four to a bank.
 constexpr int tile_ws_slot_width(int W) { return (((W + 4 + 1) >> 1) | 1) << 1; }
 constexpr int tile_ws_slot_entries(int H, int W) { return (H + 4) * tile_ws_slot_width(W); }
-constexpr int kWsAStageRow = 528;   // bytes per pixel row of the fp16 A stage (512 + 16: b128 fragment reads conflict-free)
+// Bytes per pixel row of the fp16 A stage: unpadded, the row's 32 sixteen-byte chunks at the slots of et_lds_layout.h.  (Until
+// this layout the rows were padded to 528 bytes "so that the b128 fragment reads are conflict-free" -- they are for contiguous
+// 16-lane groups; gfx950 services a ds_read_b128 in the groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, in which one lane
+// with kg = 1 landed on the slot of a lane with kg = 0: 8 LDS cycles per read instead of 4, tests/test_lds_layout_cpu.py.)
+constexpr int kWsAStageRow = ET_ASTAGE_ROW_BYTES;
 constexpr int kWsColWords = 72;     // column masks: 64 columns + 2 pad words on either side (+ 4 unused)
 constexpr unsigned kWsColOvf = 0x80000000u;   // a tap outside the column's 16-row window
 // Maps above 64 x 64 (BT = true, 288-row arrays: 96 x 96): a whole-map slot table would be 2 x 20 KB there and the block is at
@@ -114,7 +120,7 @@ constexpr size_t tile_ws_lds_bytes(int rows, int H, int W, bool band_table = fal
     return (size_t)(2 * kTilePix * (rows + 4)          /* D/B ping, pong (row stride rows + 4: 16-byte aligned rows) */
                     + kWsSlots * rows + kWsSlots * kTilePix + kWsSlots * kTilePix * 4 + 16 + 2 * kTilePix + 4 * kWsSlots + 4 + 2 * kTilePix +
                     (band_table ? kWsColWordsBand : kWsColWords)) * 4 +
-           (size_t)2 * 2 * kTilePix * kWsAStageRow + 16 +                 /* two A stages: fp16 hi, lo (16-byte aligned) */
+           (size_t)2 * 2 * kTilePix * kWsAStageRow + 256 +                /* two A stages: fp16 hi, lo (256-byte aligned) */
            (size_t)2 * (band_table ? kWsBandEntries : ((tile_ws_slot_entries(H, W) + 1) & ~1)) * 2;   /* slot tables, 16 bit */
 }
 
@@ -226,12 +232,13 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
     unsigned short *s_slot = reinterpret_cast<unsigned short *>(s_col + kColWords);  // [2][slot_entries]
     // (offset arithmetic, not pointer rounding: a pointer that went through an integer comes back as a generic one and
     //  every access through it becomes a FLAT load, which also ties up the vector-memory counter)
-    const int ahi_off = (int)(((reinterpret_cast<char *>(s_slot + 2 * slot_entries) - reinterpret_cast<char *>(s_dyn)) + 15) & ~15);
+    // (a multiple of 256 bytes: G1 steps through a row's chunks by XOR on the whole offset, et_astage_kstep_xor)
+    const int ahi_off = (int)(((reinterpret_cast<char *>(s_slot + 2 * slot_entries) - reinterpret_cast<char *>(s_dyn)) + 255) & ~255);
     // TWO A stages (tile j uses stage j & 1) since round 6: the (x, y) sample table that used to take these 32 KB is in registers,
     // and with a stage of its own the A tile of T_{i+1} can be written while G1(T_i) reads the other one -- see kCopyInA.
     constexpr int kAStageBytes = 2 * kTilePix * kWsAStageRow;
-    char *s_ahi = reinterpret_cast<char *>(s_dyn) + ahi_off;                // [2] x { [32][528 B] fp16 hi of the scaled A tile,
-    char *s_alo = s_ahi + kTilePix * kWsAStageRow;                          //         [32][528 B] fp16 lo }
+    char *s_ahi = reinterpret_cast<char *>(s_dyn) + ahi_off;                // [2] x { [32][512 B] fp16 hi of the scaled A tile,
+    char *s_alo = s_ahi + kTilePix * kWsAStageRow;                          //         [32][512 B] fp16 lo }
     // KH == 2: ONE A stage (both halves of a tile multiply the same reference rows); the second stage's bytes are the stash of
     // the first half's G2 accumulators: 8 KB per matrix wave, a lane's registers at lane-private addresses (no exchange)
     auto astage_of = [&](int j) { return KH == 2 ? 0 : (j & 1); };
@@ -309,11 +316,16 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
     //   * Loads.  The load path merges the addresses of a lane QUAD only (scripts/micro/load_patterns.hip: an
     //     instruction whose quads each read 64 contiguous bytes runs at 32-40 B/clk per CU; in operand order -- lane
     //     n = row n, so neighbouring lanes are 1 KB apart -- it is 15 B/clk, and G1 was bound by exactly that:
-    //     192 KB per tile = 12 k cycles).  So a lane LOADS 16 bytes of row (lane >> 2), chunk (lane & 3) of a
-    //     64-byte segment: two instructions (segments e = 0, 1) per 16-row unit and 32-channel k-step.
+    //     192 KB per tile = 12 k cycles).  So a lane LOADS 16 bytes of row (lane >> 2), one chunk of a 64-byte segment
+    //     (chunk lane & 3 for rows 0-7 of the unit, (lane & 3) ^ 2 for rows 8-15: et_g1_loaded_chunk): two instructions
+    //     (segments e = 0, 1) per 16-row unit and 32-channel k-step.
     //   * Operand order.  The MFMA wants lane (n, kg) = (lane & 15, lane >> 4) to hold eight k-values of row n: the
     //     loaded registers are rearranged with ds_bpermute (the LDS crossbar, no LDS memory; lane (n, kg) takes the
-    //     registers of lane 4 n + kg: ONE address for all sixteen registers of a k-step).  Lane (n, kg) then holds
+    //     registers of the lane that loaded chunk kg of row n, et_g1_source_lane: ONE address for all sixteen registers
+    //     of a k-step.  The chunk order of rows 8-15 makes the 32 sources of a half-wave distinct mod 32: with 4 n + kg
+    //     throughout they were two to a residue, which SQ_LDS_BANK_CONFLICT counts -- 2.2e7 per launch of the headline
+    //     shape, profiles/lds_layout_ab.txt -- although the instruction takes the same time for every pattern,
+    //     scripts/micro/bpermute_patterns.hip).  Lane (n, kg) then holds
     //     channels 32 ks + 16 e + 4 kg + w (e, w = segment, word); the k order is ours to choose -- the fp16 A stage
     //     is written in the same order (copy_finish), so the A fragments stay single 16-byte LDS reads.
     //   * B rows go through a ring of kD1 k-steps of registers that runs across the wave's units; the first ring
@@ -335,7 +347,7 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
             const int unit = wave + 4 * ui;
             boff[ui] = kOob;
             if (U > 0 && unit < ((U + 15) >> 4))
-                boff[ui] = s_rows[slot * ROWS + min(unit * 16 + (lane >> 2), U - 1)] * kRowBytes + (lane & 3) * 16;
+                boff[ui] = s_rows[slot * ROWS + min(unit * 16 + (lane >> 2), U - 1)] * kRowBytes + et_g1_loaded_chunk(lane) * 16;
         }
         const int n = valid ? tile_of(j) / tp.tiles_per_pair : 0;
         const __amdgpu_buffer_rsrc_t src = make_rsrc(p.fsrc + (size_t)n * HW * C, map_bytes);
@@ -357,9 +369,11 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
         if (wave >= nunits) return;
         float *dst = s_arr + (j & 1) * kArr;
         float amax = 0.f;
-        const int paddr = (4 * (lane & 15) + (lane >> 4)) * 4;
-        const char *ahp = s_ahi + astage_of(j) * kAStageBytes + (lane & 15) * kWsAStageRow + (lane >> 4) * 16;
-        const char *alp = s_alo + astage_of(j) * kAStageBytes + (lane & 15) * kWsAStageRow + (lane >> 4) * 16;
+        const int paddr = et_g1_source_lane(lane & 15, lane >> 4) * 4;
+        // this lane's chunk (k-step 0, k-group lane >> 4) of pixel row lane & 15, as an offset into the block's LDS; the chunk of
+        // k-step ks is at that offset ^ et_astage_kstep_xor(ks) (one XOR per k-step; rows + 16 and the lo stage: constants)
+        const int aoff = ahi_off + astage_of(j) * kAStageBytes + et_astage_off(lane & 15, 0, lane >> 4);
+        constexpr int kALo = kTilePix * kWsAStageRow;
         // straight-line over the units and their k-steps, forward exits only (exact vmcnt waits, see G2)
         // Round 6: the LDS stage of a k-step -- eight ds_bpermute of the loaded B registers, four fragment reads of the A stage --
         // is issued ONE k-step ahead, into a second set of registers (24 more).  Until then every k-step began with those twelve
@@ -377,10 +391,11 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
                 pvd[4 * e + 2] = __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(x.z)));
                 pvd[4 * e + 3] = __int_as_float(__builtin_amdgcn_ds_bpermute(paddr, __float_as_int(x.w)));
             }
+            const char *ap = reinterpret_cast<const char *>(s_dyn) + (aoff ^ et_astage_kstep_xor(ks));
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
-                ah[g] = *reinterpret_cast<const f16x8 *>(ahp + g * 16 * kWsAStageRow + ks * 64);
-                al[g] = *reinterpret_cast<const f16x8 *>(alp + g * 16 * kWsAStageRow + ks * 64);
+                ah[g] = *reinterpret_cast<const f16x8 *>(ap + g * 16 * kWsAStageRow);
+                al[g] = *reinterpret_cast<const f16x8 *>(ap + g * 16 * kWsAStageRow + kALo);
             }
         };
         lds_stage(0, pv[0], afh[0], afl[0]);
@@ -509,10 +524,11 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
             split_f16_pair(v[2], v[3], h1, l1);
             typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
             const f16x4 hi = __builtin_bit_cast(f16x4, u32x2_t{h0, h1}), lo = __builtin_bit_cast(f16x4, u32x2_t{l0, l1});
-            // (the lane's channels 4 lane .. + 3 = 32 ks + 16 e + 4 kg + w go to fp16 position 32 ks + 8 kg + 4 e + w: G1's k order)
-            const int apos = (lane >> 3) * 64 + (lane & 3) * 16 + ((lane >> 2) & 1) * 8;
-            *reinterpret_cast<f16x4 *>(s_ahi + astage_of(jc) * kAStageBytes + (cfirst + ii) * kWsAStageRow + apos) = hi;
-            *reinterpret_cast<f16x4 *>(s_alo + astage_of(jc) * kAStageBytes + (cfirst + ii) * kWsAStageRow + apos) = lo;
+            // (the lane's channels 4 lane .. + 3 = 32 ks + 16 e + 4 kg + w go to fp16 position 32 ks + 8 kg + 4 e + w: G1's k order
+            // = half e of the row's chunk (ks, kg) = (lane >> 3, lane & 3), at the chunk's slot of et_lds_layout.h)
+            const int apos = et_astage_off(cfirst + ii, lane >> 3, lane & 3) + ((lane >> 2) & 1) * 8;
+            *reinterpret_cast<f16x4 *>(s_ahi + astage_of(jc) * kAStageBytes + apos) = hi;
+            *reinterpret_cast<f16x4 *>(s_alo + astage_of(jc) * kAStageBytes + apos) = lo;
             if (lane == 0) s_ainv[astage_of(jc) * kTilePix + cfirst + ii] = s_inv;
         }
         if (p.res_base) {
@@ -664,8 +680,10 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
             // epipolar.py:250-253, resnet.py:388), the tile's 32 rows x this wave's 64 output channels ----
             // The out tile goes through LDS as fp16 hi | lo (the contraction runs over ALL 256 channels of out, i.e. over
             // the four waves' accumulators): into the B rows G2 has just consumed -- 32 rows x 512 B of hi, then of lo, the
-            // 16-byte chunks of a row XOR-swizzled by the row so that the fragment reads below (32 rows x one chunk) are
-            // conflict-free without padding (the buffer is 32 x 1040 B: two padded stages would not fit).  Scale: the pair's
+            // 16-byte chunks of a row XOR-swizzled by the row (et_g3_stage_off: by m & 15 -- a lane group of the fragment reads
+            // below holds sixteen different rows; m & 7, until this layout, put two of them on every slot: 8 LDS cycles per read
+            // instead of 4) so that those reads are conflict-free without padding (the buffer is 32 x 1040 B: two padded stages
+            // would not fit).  Scale: the pair's
             // s_src -- out is a convex combination of source rows that passed the fp16 guard, so |out s_src| < 2^15.
             // Two barriers among the matrix waves: every wave is done reading the B rows / every wave has written its part.
             char *stage = reinterpret_cast<char *>(s_arr + (j & 1) * kArr);
@@ -683,7 +701,9 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
             // k-step waited ~200 cycles for its fragments -- 3 k of the ~7.6 k cycles G3 adds to a tile.  The registers come from
             // the feat rows: they are loaded LATE, at k-steps 12 and 13, into what the ring no longer refills (behind the loop
             // their latency was exposed whole: 1-2 % slower in round 4; before the loop they cost the ring its depth).
-            constexpr int kRing3 = 4;
+            // THREE deep since the A fragments are read a k-step ahead (8 more registers: with four the fused instances spill
+            // 52-60 bytes per lane); round 6 measured three and four as equal, the feat rows now load at k-steps 13 and 14.
+            constexpr int kRing3 = 3;
             u32x4 bq[kRing3][4];      // [k-step mod kRing3][2 nb + term]
             const int woff = (wave * 2) * 2 * 1024 + lane * 16;     // fragment (ks, nb = 2 wave, hi) of this lane, bytes
             auto wload = [&](int ks, u32x4 (&dst)[4]) {
@@ -703,7 +723,7 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
                     const int m = (r & 3) + 8 * (r >> 2) + 4 * lh3;
                     unsigned hh, ll;
                     split_f16_pair(acc0[r] * k, acc1[r] * k, hh, ll);
-                    const int off = m * 512 + (((cb >> 3) ^ (m & 7)) << 4) + (cb & 7) * 2;
+                    const int off = et_g3_stage_off(m, cb >> 3) + (cb & 7) * 2;
                     *reinterpret_cast<unsigned *>(stage + off) = hh;
                     *reinterpret_cast<unsigned *>(stage + 16384 + off) = ll;
                 }
@@ -728,13 +748,21 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
             for (int r = 0; r < 16; ++r) g0[r] = g1[r] = 0.f;
             mb_target += kWsMatrixWaves;
             matrix_barrier(s_U + 5, mb_target, lane, tp.err);
-            const char *sp = stage + li * 512;
+            // The A fragments of a k-step are read ONE k-step ahead, into a second pair of registers (as G1's LDS stage): the
+            // vector waves are at the barrier while the matrix waves run G3, so nothing else on the SIMD covers the latency of
+            // a read issued right in front of the MFMAs that consume it.
+            f16x8 ga[2][2];      // [k-step & 1][hi, lo]
+            auto g3_frag = [&](int ks, f16x8 (&d)[2]) {     // A[m = li][k = 16 ks + 8 lh .. + 7]: chunk 2 ks + lh of row li
+                const char *sp = stage + et_g3_stage_off(li, 2 * ks + lh);
+                d[0] = *reinterpret_cast<const f16x8 *>(sp);
+                d[1] = *reinterpret_cast<const f16x8 *>(sp + 16384);
+            };
+            g3_frag(0, ga[0]);
 #pragma unroll
             for (int ks = 0; ks < 16; ++ks) {
-                // A[m = li][k = 16 ks + 8 lh .. + 7]: chunk 2 ks + lh of row li
-                const int ch = ((2 * ks + lh) ^ (li & 7)) << 4;
-                const f16x8 ah = *reinterpret_cast<const f16x8 *>(sp + ch);
-                const f16x8 al = *reinterpret_cast<const f16x8 *>(sp + 16384 + ch);
+                if (ks + 1 < 16) g3_frag(ks + 1, ga[(ks + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+                const f16x8 ah = ga[ks & 1][0], al = ga[ks & 1][1];
                 u32x4(&bb)[4] = bq[ks % kRing3];
                 g0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, __builtin_bit_cast(f16x8, bb[0]), g0, 0, 0, 0);
                 g0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, __builtin_bit_cast(f16x8, bb[1]), g0, 0, 0, 0);

@@ -3,7 +3,8 @@
 
 Needs a profiling build of the library:  ET_EXTRA_HIPCC_FLAGS=-DET_WS_PROFILE python -m epipolar_transformers_amd.build
 (force a rebuild of et_forward_tile.hip).  The kernel then accumulates s_memtime deltas per pipeline segment and
-wave; this script prints their per-tile means on the Config-2 batch."""
+wave; this script prints their per-tile means on the Config-2 batch.  PROF_KERNEL=fused: the one-kernel layer (its G3 is part
+of the matrix waves' "G2" segment)."""
 import ctypes
 import os
 import sys
@@ -29,11 +30,16 @@ src = torch.randn(128, H, H, C, device=dev, generator=g).relu_()
 cam = camera.pair_algebra(P1, P2).to(dev)
 spec = ops.LayerSpec(H=H, W=H, K=K, variant=variant)
 bias = torch.randn(C, device=dev)
+if os.environ.get("PROF_KERNEL") == "fused":
+    packed = ops.residual_gemm_pack(torch.randn(C, C, device=dev, generator=g) * 0.05 + torch.eye(C, device=dev))
+    run = lambda: ops.forward_fused_nhwc(spec, ref, src, cam, packed, bias)
+else:
+    run = lambda: ops.forward_nhwc(spec, ref, src, cam, res_bias=bias, want_res_base=True)
 for _ in range(3):
-    ops.forward_nhwc(spec, ref, src, cam, res_bias=bias, want_res_base=True)
+    run()
 prof = torch.zeros(256 * (4 + nv) * 12, dtype=torch.int64, device=dev)
 raw.et_dev_ws_profile(ctypes.c_void_p(prof.data_ptr()))
-ops.forward_nhwc(spec, ref, src, cam, res_bias=bias, want_res_base=True)
+run()
 torch.cuda.synchronize()
 raw.et_dev_ws_profile(None)
 p = prof.cpu().numpy().reshape(256, 4 + nv, 12).astype(np.float64) / 64.0      # cycles per tile (64 tiles per block)
