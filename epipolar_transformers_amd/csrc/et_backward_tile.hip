@@ -11,23 +11,20 @@ namespace {
 }  // namespace
 
 namespace {
-// Workspace of the deterministic form: the forward-layout workspace (same header, same sticky error word), then, from the next
-// 256-byte boundary: acc int64[N * HW * 256] | quanta float[4 * N] | partial maxima float[4 * kDetMaxBlocks * N].
+// Workspace of the deterministic form: the forward-layout workspace (same header, same sticky error word), then the tail of
+// et_tile_layout.h's det_workspace_layout: acc | quanta | partial maxima.
 struct DetWorkspace {
     long long *acc;
     float *quanta, *partial;
 };
-size_t det_extra_bytes(size_t pairs, size_t hw)
+size_t det_extra_bytes(size_t pairs, size_t hw) { return det_workspace_layout(0, pairs, hw).extra_bytes; }
+DetWorkspace carve_det_workspace(const TileWorkspace &w, size_t pairs, size_t hw)
 {
-    return 256 + pairs * hw * 256 * sizeof(long long) + pairs * 4 * sizeof(float) + pairs * kDetMaxBlocks * 4 * sizeof(float);
-}
-DetWorkspace carve_det_workspace(const TileWorkspace &w, size_t tiles, size_t pairs, size_t hw)
-{
+    const DetWorkspaceLayout l = det_workspace_layout(w.end, pairs, hw);
     DetWorkspace dw;
-    const uintptr_t end = reinterpret_cast<uintptr_t>(w.ovf_count) + tile_workspace_words(tiles, pairs, hw) * sizeof(int);
-    dw.acc = reinterpret_cast<long long *>((end + 255) & ~(uintptr_t)255);
-    dw.quanta = reinterpret_cast<float *>(dw.acc + pairs * hw * 256);
-    dw.partial = dw.quanta + 4 * pairs;
+    dw.acc = reinterpret_cast<long long *>(w.base + l.acc);
+    dw.quanta = reinterpret_cast<float *>(w.base + l.quanta);
+    dw.partial = reinterpret_cast<float *>(w.base + l.partial);
     return dw;
 }
 int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
@@ -190,7 +187,7 @@ int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, cons
     tp.scales = w.scales;
     // deterministic form: the clearing blocks zero the int64 accumulator instead (twice the bytes); grad_src is written whole by
     // det_finish_kernel
-    const DetWorkspace dw = carve_det_workspace(w, (size_t)c.total, (size_t)desc->N, (size_t)HW);
+    const DetWorkspace dw = carve_det_workspace(w, (size_t)desc->N, (size_t)HW);
     const size_t clear_vec4 = (size_t)desc->N * HW * (desc->C / 4) * (det ? 2 : 1);     // (C == 256)
     // (header = true: the ordering clears the workspace's overflow counter, which the merged launch below counts into)
     if (int e = launch_tile_order(desc, xs, ys, cam, feat_ref, feat_src, w, c.tiles_per_pair, true, w.scales, false,

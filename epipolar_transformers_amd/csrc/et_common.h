@@ -18,6 +18,8 @@
 //     both tile units:    kernels_tile_order.inc     the ordering of a tile call (sort keys, one bitonic sort per pair)
 //                         kernels_tile_common.inc    device helpers of both directions: taps, array rows, the tile GEMMs
 //                         et_tile_host.h             the host side of a tile call: checks, workspace, ordering, launch
+//                         et_tile_layout.h           the tile path's memory formats: workspace header words and regions, the
+//                                                    kernels' LDS layouts (plain constexpr C++, also built by a host test)
 //   et_residual_gemm.hip  kernels_residual_gemm.inc  x = feat + bias + out . Wf^T as a split-fp16 GEMM, and the z branch's
 //                                                    batch statistics / backward (et_residual_gemm, et_z_*)
 //   et_misc.hip           kernels_misc.inc           sample_locs, residual epilogue, NCHW <-> NHWC, ABI version / errors

@@ -69,7 +69,7 @@ TileWsParams tile_ws_params(const FwdParams &f, const TileCall &c)
     wp.bias = nullptr;
     wp.x = nullptr;
     wp.err = c.w.err;
-    wp.tile_ctr = c.w.ovf_count + 2;
+    wp.tile_ctr = c.w.ovf_count + kTileHdrXcdCtr;
     wp.setprio = 0;
     wp.prof = nullptr;
     return wp;
@@ -149,20 +149,20 @@ size_t et_epipolar_forward_workspace_bytes(const EtLayerDesc *desc)
 {
     if (validate(desc) || !tile_eligible(desc)) return 0;
     const size_t tiles = (size_t)desc->N * (((size_t)desc->H * desc->W + kTilePix - 1) / kTilePix);
-    return tile_workspace_words(tiles, (size_t)desc->N, (size_t)desc->H * desc->W) * sizeof(int) + 256u;
+    return tile_workspace_layout(tiles, (size_t)desc->N, (size_t)desc->H * desc->W).bytes;
 }
 
 size_t et_epipolar_forward_workspace_error_offset(const EtLayerDesc *desc)
 {
     if (validate(desc) || !tile_eligible(desc)) return 0;
-    return sizeof(int);   // word 1 of the header: the same place for every shape (a workspace is reused across shapes)
+    return kTileHdrErr * sizeof(int);   // in the header: the same place for every shape (a workspace is reused across shapes)
 }
 
 size_t et_epipolar_forward_workspace_stats_offset(const EtLayerDesc *desc)
 {
     if (validate(desc) || !tile_eligible(desc)) return 0;
     const size_t tiles = (size_t)desc->N * (((size_t)desc->H * desc->W + kTilePix - 1) / kTilePix);
-    return (kTileWorkspaceHeaderWords + tiles * kTilePix + tiles) * sizeof(int);
+    return tile_workspace_layout(tiles, (size_t)desc->N, (size_t)desc->H * desc->W).stats;
 }
 
 int et_epipolar_forward_tiled(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,

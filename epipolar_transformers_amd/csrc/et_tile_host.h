@@ -4,8 +4,10 @@
 #pragma once
 #include <algorithm>
 #include "et_common.h"
+#include "et_tile_layout.h"         // kTilePix, kTileRows*, the workspace's header words and regions, the kernels' LDS
 namespace {
-#include "kernels_tile_order.inc"   // kTilePix, kTileRows*, tile_keys_kernel, tile_order_kernel
+static_assert(kTileWave == kWave && kTileXcds == kXcds, "et_tile_layout.h restates them (it includes no HIP header)");
+#include "kernels_tile_order.inc"   // tile_keys_kernel, tile_order_kernel
 
 // The MFMA tile path applies to the 256-channel head when one reference pixel alone can never
 // overflow the tile's row array: a pixel's K samples touch at most 4K source pixels, and a line
@@ -59,50 +61,30 @@ bool tile_ws_eligible(const EtLayerDesc *d)
     return (!(d->variant & ET_VARIANT_TILE_CLASSIC) && d->softmax_enabled && d->K <= 64 && d->W >= 2 &&
             tile_rows(d) == kTileRowsSmall) || tile_ws_band(d);
 }
-// Workspace of the tile forward (all int32, base aligned up to 256 bytes):
-//   header (64 words): [0] overflow count, [1] sticky error word -- at the front, so that their offsets do not depend on
-//   the shape of the call (a workspace is reused across shapes) |
-//   perm[tiles * 32] | overflow list[tiles] | stats[tiles] | scales[4 * N] (float) |
-//   segments[tiles * 32] (float4, 16-byte aligned; in tile order.  Until tile_order_kernel writes them the region of a pair
-//   holds the pair's sort keys: 8 bytes per pixel, tile_keys_kernel) |
-//   band[tiles] (float4: the tile's base line, warp-specialised kernel) | segments by pixel[N * HW] (float4)
-// Header words beyond [0] / [1] are scratch of the kernels of ONE call, cleared by tile_keys_kernel (`header`) at its start:
-//   forward:  [2 .. 9]  one tile counter per XCD (the blocks of an XCD draw their tiles from it)
-//   backward: [2] four-group tiles met so far, [3] eight-or-more-group tiles met early (kernels_backward_tile.inc: the merged
-//             kernel splits the first 128 / 32 of a call in place and defers the rest to its second launch), [4] over-capacity
-//             tiles met so far (beyond the first 256 of a call they are deferred without a search)
-//   deterministic backward (et_epipolar_backward_tiled_det): [0] deferred tiles that fit the second launch's kernel whole (listed from
-//             the front of the overflow list), [2] those that do not (listed from its back, eight blocks each); [3], [4] unused --
-//             which tile goes where is a function of the tile alone.  Behind the forward layout, from the next 256-byte boundary:
-//             int64 accumulator[N * HW * 256] | quanta[4 * N] | partial maxima[4 * 32 * N]  (et_backward_tile.hip)
-// The backward REUSES the forward's counter words: safe because every call starts with the ordering kernels on the same stream,
-// which zero them -- a change to either user has to keep that.  Which over-capacity tiles a backward call splits in
-// place and which it defers depends on the order its blocks reach those counters and on blockIdx relative to gridDim: the
-// SET of deferred tiles, and with it the order of the float-atomic additions into grad_src, differs from run to run
-// (gradients reproducible to rounding, as documented; ops.backward_deferred_tiles() counts vary by a few tiles).
+// The caller's workspace, carved: header words, regions and sizes are et_tile_layout.h's.
 struct TileWorkspace {
     int *perm, *ovf_count, *err, *ovf_list, *stats;
     float *scales;
     float4 *segs, *band, *segs_pix;
+    char *base;     // the aligned base: the offsets of a layout count from here
+    size_t end;     // TileWorkspaceLayout::end of this call's shape
 };
-constexpr size_t kTileWorkspaceHeaderWords = 64;
-size_t tile_workspace_words(size_t tiles, size_t pairs, size_t hw)
-{
-    return kTileWorkspaceHeaderWords + tiles * kTilePix + 2 * tiles + 4 * pairs + 4 + 4 * tiles * kTilePix + 4 * tiles +
-           4 * pairs * hw;
-}
 TileWorkspace carve_tile_workspace(void *workspace, size_t tiles, size_t pairs, size_t hw)
 {
+    const TileWorkspaceLayout l = tile_workspace_layout(tiles, pairs, hw);
     TileWorkspace w;
-    w.ovf_count = reinterpret_cast<int *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    w.err = w.ovf_count + 1;
-    w.perm = w.ovf_count + kTileWorkspaceHeaderWords;
-    w.ovf_list = w.perm + tiles * kTilePix;
-    w.stats = w.ovf_list + tiles;
-    w.scales = reinterpret_cast<float *>(w.stats + tiles);
-    w.segs = reinterpret_cast<float4 *>((reinterpret_cast<uintptr_t>(w.scales + 4 * pairs) + 15) & ~(uintptr_t)15);
-    w.band = w.segs + tiles * kTilePix;
-    w.segs_pix = w.band + tiles;
+    w.base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + (kTileWorkspaceAlign - 1)) & ~(uintptr_t)(kTileWorkspaceAlign - 1));
+    w.end = l.end;
+    int *const header = reinterpret_cast<int *>(w.base);
+    w.ovf_count = header + kTileHdrCount;
+    w.err = header + kTileHdrErr;
+    w.perm = reinterpret_cast<int *>(w.base + l.perm);
+    w.ovf_list = reinterpret_cast<int *>(w.base + l.ovf_list);
+    w.stats = reinterpret_cast<int *>(w.base + l.stats);
+    w.scales = reinterpret_cast<float *>(w.base + l.scales);
+    w.segs = reinterpret_cast<float4 *>(w.base + l.segs);
+    w.band = reinterpret_cast<float4 *>(w.base + l.band);
+    w.segs_pix = reinterpret_cast<float4 *>(w.base + l.segs_pix);
     return w;
 }
 
@@ -121,6 +103,8 @@ int launch_tile_order(const EtLayerDesc *desc, const float *xs, const float *ys,
     const size_t lds_sort = tile_order_lds_bytes(n2);
     const int dev = current_device();
     ET_GRANT_LDS(tile_order_kernel, lds_sort, dev);
+    // (the sort keys of a pair, 8 bytes per pixel, live in the region of its ordered segments until tile_order_kernel has
+    //  consumed them: et_tile_layout.h)
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(w.segs);
     hipLaunchKernelGGL(tile_keys_kernel, dim3((unsigned)((HW + 255) / 256) * desc->N), dim3(256), 0, st, *desc, xs, ys, cam, perm_stride,
                        keys, w.segs_pix, header ? w.ovf_count : (int *)nullptr);
@@ -151,7 +135,7 @@ int begin_tile_call(const EtLayerDesc *desc, const char *who, const char *bad_ar
     c->HW = desc->H * desc->W;
     c->tiles_per_pair = (c->HW + kTilePix - 1) / kTilePix;
     const long long total = (long long)c->tiles_per_pair * desc->N;
-    const size_t need = tile_workspace_words((size_t)total, (size_t)desc->N, (size_t)c->HW) * sizeof(int) + 256u +
+    const size_t need = tile_workspace_layout((size_t)total, (size_t)desc->N, (size_t)c->HW).bytes +
                         (extra_bytes ? extra_bytes((size_t)desc->N, (size_t)c->HW) : 0);
     if (!workspace || workspace_bytes < need)
         return fail("%s: workspace of %zu bytes is smaller than the %zu required", who, workspace ? workspace_bytes : (size_t)0, need);

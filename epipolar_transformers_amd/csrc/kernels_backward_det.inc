@@ -30,7 +30,7 @@
 // A contribution of 2^48 quanta or more (or a NaN) cannot happen under the bound; the tile kernel checks it all the same, ORs
 // kDetGuardMask (bit 2) into the workspace's sticky error word and does not add it.
 
-constexpr int kDetMaxBlocks = 32;       // blocks per pair of det_maxima_kernel (one partial result each)
+// (kDetMaxBlocks, the blocks per pair of det_maxima_kernel -- one partial result each: et_tile_layout.h)
 constexpr int kDetQuantumMinExp = -100;     // (an fp32 bound gives at most 2^81: no upper clamp is needed)
 
 struct DetQuantum {

@@ -33,27 +33,10 @@
 #pragma once
 #include "kernels_tile_common.inc"   // taps_of, row_runs / scatter_row, tile_gemm_* (and et_split_f16.h)
 
-// Row-array widths of the merged form (two arrays): 192 columns for maps up to 64 x 64 (three blocks per CU), 288 for
-// maps up to 96 x 96 (two, as the one-array kernel there); tiles with more rows are split into pixel groups.
-constexpr int kTileRowsMerged = 192, kTileRowsMergedLarge = 288;
-constexpr bool bwd_rows_merged(int rows) { return rows == kTileRowsMerged || rows == kTileRowsMergedLarge; }
-// floats of the array region: one array (which also stages the 32 x 260 A tile of the D-type GEMMs), or two for the
-// merged form
-constexpr int bwd_tile_array_floats(int rows);
 template <int ROWS> struct kArrayFloatsOf { static constexpr int value = bwd_tile_array_floats(ROWS); };
-constexpr int bwd_tile_array_floats(int rows)
-{
-    return bwd_rows_merged(rows)
-               ? (2 * kTilePix * (rows + 1) > tile_array_floats(rows) ? 2 * kTilePix * (rows + 1) : tile_array_floats(rows))
-               : tile_array_floats(rows);
-}
-// dynamic LDS of a block of ROWS = rows and KPL = kpl: what bwd_tile_body carves out of s_dyn -- the array(s), s_rows, s_pix,
-// s_misc[60], s_seg, bitmap + prefix of hw_words words each and, where the kernel keeps it (TAB), the table of sample locations
-constexpr size_t bwd_tile_lds_bytes(int rows, int hw_words, int kpl)
-{
-    return (size_t)(bwd_tile_array_floats(rows) + rows + kTilePix + 60 + kTilePix * 4) * 4 + (size_t)hw_words * 8 +
-           ((kpl == 1 && !bwd_rows_merged(rows)) ? (size_t)kTilePix * kWave * 8 : 0);
-}
+// dynamic LDS of a block of ROWS = rows and KPL = kpl: et_tile_layout.h's layout, which bwd_tile_body's pointers are asserted
+// against
+constexpr size_t bwd_tile_lds_bytes(int rows, int hw_words, int kpl) { return (size_t)bwd_tile_lds(rows, hw_words, kpl).end; }
 
 struct BwdTileParams {
     BwdParams b;
@@ -133,8 +116,21 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
     float *s_D2 = s_D + kTilePix * kTileStride;                          // MERGED: [32][ROWS+1]  B beside Bs
     int *s_rows = reinterpret_cast<int *>(s_D + kArrayFloats);           // [ROWS] slot -> source pixel
     int *s_pix = s_rows + kTileRowsMax;                                  // [32]  tile pixel ids
-    int *s_misc = s_pix + kTilePix;                                      // [4]   U, ... ; [4..19] block reductions ; [20..51] A-row scales
-    float *s_seg = reinterpret_cast<float *>(s_misc + 60);               // [32][4] epipolar segments
+    int *s_misc = s_pix + kTilePix;                                      // BwdTileLds' U .. ainv, at the word indices below
+    // The regions of et_tile_layout.h's BwdTileLds.  The pointers are kept as this chain (written from the layout's offsets the
+    // backend fails to compile this kernel: "illegal VGPR to SGPR copy") and asserted against the layout instead: its constant
+    // part at hw_words = 0, and at hw_words = 7 the terms that bitmap | prefix | nxy add behind it.
+    constexpr BwdTileLds L = bwd_tile_lds(ROWS, 0, KPL), L7 = bwd_tile_lds(ROWS, 7, KPL);
+    constexpr int kMiscU = 0, kMiscGroupRows = (L.group_rows - L.U) / 4, kMiscDrawn = (L.drawn - L.U) / 4, kMiscRed2 = (L.red2 - L.U) / 4,
+                  kMiscRed1 = (L.red1 - L.U) / 4, kMiscAinv = (L.ainv - L.U) / 4, kMiscWords = (L.seg - L.U) / 4;
+    static_assert(L.arr == 0 && L.rows == kArrayFloats * 4 && L.pix == L.rows + kTileRowsMax * 4 && L.U == L.pix + kTilePix * 4 &&
+                      L.bitmap == L.seg + kTilePix * 16 && L.prefix == L.bitmap && L.nxy == L.prefix &&
+                      L.end == L.nxy + (TAB ? kTileNxyBytes : 0),
+                  "bwd_tile_body's pointers follow et_tile_layout.h");
+    static_assert(L7.bitmap == L.bitmap && L7.prefix == L7.bitmap + 7 * 4 && L7.nxy == L7.prefix + 7 * 4 &&
+                      L7.end == L7.nxy + (TAB ? kTileNxyBytes : 0),
+                  "bitmap, prefix: hw_words words each, then the table");
+    float *s_seg = reinterpret_cast<float *>(s_misc + kMiscWords);       // [32][4] epipolar segments
     unsigned *s_bitmap = reinterpret_cast<unsigned *>(s_seg + kTilePix * 4);  // [hw_words]
     int *s_prefix = reinterpret_cast<int *>(s_bitmap + tp.hw_words);     // [hw_words] exclusive popcount prefix
     f32x2 *s_nxy = reinterpret_cast<f32x2 *>(s_prefix + tp.hw_words);    // TAB: [32][64] normalised sample locations
@@ -284,10 +280,10 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
                 if (t < tp.hw_words) s_prefix[t] = carry + incl - c;
                 carry += __shfl(incl, kWave - 1);
             }
-            if (lane == 0) s_misc[0] = carry;
+            if (lane == 0) s_misc[kMiscU] = carry;
         }
         __syncthreads();
-        const int U = s_misc[0];
+        const int U = s_misc[kMiscU];
         if (U > tp.rows_cap) return false;  // block-uniform: split the tile further
         for (int t = tid; t < tp.hw_words; t += blockDim.x) {
             unsigned m = s_bitmap[t];
@@ -314,7 +310,7 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
             if constexpr (SPLIT_D) {
                 if (tp.scales && nb <= 2 * kWavesPerBlock * kSplitPasses) {
                     const bool ovf = tile_gemm_rows_split<kTileStride, kSplitPasses>(abuf, src, stage_off, s_rows, s_D,
-                                                                       reinterpret_cast<float *>(s_misc + 20), U, nb, tid, wave,
+                                                                       reinterpret_cast<float *>(s_misc + kMiscAinv), U, nb, tid, wave,
                                                                        lane, tp.scales[n * 4 + 2], tp.scales[n * 4 + 3]);
                     if (!__syncthreads_or(ovf)) return true;      // (a value beyond fp16's range: the tile again, in exact fp32)
                 }
@@ -425,7 +421,7 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
             }
             xm1 = wave_all_max(xm1);
             xm2 = wave_all_max(xm2);
-            float *s_red = reinterpret_cast<float *>(s_misc + 4);
+            float *s_red = reinterpret_cast<float *>(s_misc + kMiscRed2);
             if (lane == 0) {                                  // (block barriers separate the uses of s_red)
                 s_red[wave] = xm1;
                 s_red[4 + wave] = xm2;
@@ -735,7 +731,7 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
                 const float *xr = s_D + (tid >> 3) * kTileStride;
                 for (int c = tid & 7; c < ucols; c += 8) xm = fmaxf(xm, fabsf(xr[c]));
                 xm = wave_all_max(xm);
-                float *s_red = reinterpret_cast<float *>(s_misc + 12);
+                float *s_red = reinterpret_cast<float *>(s_misc + kMiscRed1);
                 if (lane == 0) s_red[wave] = xm;
                 __syncthreads();
                 const float sa = pow2_scale_capped(fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3])));
@@ -835,7 +831,7 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
     auto rows_of_group = [&](int g, int gsize) {
         __syncthreads();
         for (int t = tid; t < tp.hw_words; t += blockDim.x) s_bitmap[t] = 0u;
-        if (tid == 0) s_misc[1] = 0;
+        if (tid == 0) s_misc[kMiscGroupRows] = 0;
         __syncthreads();
 #pragma unroll 1
         for (int ii = 0; ii < PW; ++ii) {
@@ -852,9 +848,9 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
         __syncthreads();
         int cnt = 0;
         for (int t = tid; t < tp.hw_words; t += blockDim.x) cnt += __popc(s_bitmap[t]);
-        if (cnt) atomicAdd(&s_misc[1], cnt);
+        if (cnt) atomicAdd(&s_misc[kMiscGroupRows], cnt);
         __syncthreads();
-        return s_misc[1];
+        return s_misc[kMiscGroupRows];
     };
     const bool whole = nparts == 1 && run_group(0, kTilePix, std::true_type());
     if (!whole) {
@@ -866,13 +862,13 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
         if constexpr (DET && MERGED) {
             // Deterministic merged launch: EVERY tile that does not fit whole goes to the second launch -- no counter, no block
             // index decides.  One that fits that launch's kernel whole (U <= list_cap) is listed from the front (count: header
-            // word 0); a larger one from the back (count: header word 2, cleared by the ordering kernel) and is shared there by
+            // word kTileHdrCount); a larger one from the back (count: kTileHdrDetHard, cleared by the ordering kernel) and is shared there by
             // kDetHardParts blocks, each splitting its own pixels by the plain search.  Both are functions of the tile alone; only
             // the order of the entries varies.  Nothing has been added yet.
             if (tp.ovf_list) {
                 if (tid == 0) {
-                    if (s_misc[0] <= tp.list_cap) tp.ovf_list[atomicAdd(tp.ovf_count, 1)] = vb;
-                    else tp.ovf_list[tp.b.total_blocks - 1 - atomicAdd(tp.ovf_count + 2, 1)] = vb;
+                    if (s_misc[kMiscU] <= tp.list_cap) tp.ovf_list[atomicAdd(tp.ovf_count, 1)] = vb;
+                    else tp.ovf_list[tp.b.total_blocks - 1 - atomicAdd(tp.ovf_count + kTileHdrDetHard, 1)] = vb;
                 }
                 return;
             }
@@ -913,9 +909,9 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
             // (2.92 against 2.21 ms) -- and the second launch is now a merged kernel of 288 columns (64 x 64 maps), which takes a
             // 193..288-row tile whole at 0.18 us against two group runs of 0.135 here.  So beyond the first kBwdInPlaceTiles
             // over-capacity tiles of a call nothing is searched or split: deferred at once.
-            if (tid == 0) s_misc[3] = atomicAdd(tp.ovf_count + 4, 1);          // (header word 4: cleared by the ordering kernel)
+            if (tid == 0) s_misc[kMiscDrawn] = atomicAdd(tp.ovf_count + kTileHdrBwdOverCap, 1);   // (cleared by the ordering kernel)
             __syncthreads();
-            if (s_misc[3] >= kBwdInPlaceTiles) {
+            if (s_misc[kMiscDrawn] >= kBwdInPlaceTiles) {
                 if (tid == 0) tp.ovf_list[atomicAdd(tp.ovf_count, 1)] = vb;
                 return;
             }
@@ -929,9 +925,9 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
 #pragma unroll 1
             for (int g = 0; g < 4 && quarters; ++g) quarters = rows_of_group(g, kQuarter) <= tp.rows_cap;
             if (quarters) {
-                if (tid == 0) s_misc[3] = atomicAdd(tp.ovf_count + 2, 1);      // (header word 2: cleared by the ordering kernel)
+                if (tid == 0) s_misc[kMiscDrawn] = atomicAdd(tp.ovf_count + kTileHdrBwdQuads, 1);   // (cleared by the ordering kernel)
                 __syncthreads();
-                if (s_misc[3] < 128) {
+                if (s_misc[kMiscDrawn] < 128) {
 #pragma unroll 1
                     for (int g = 0; g < 4; ++g) run_group(g, kQuarter, std::false_type());
                     return;
@@ -950,9 +946,9 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
 #pragma unroll 1
                 for (int g = 0; g < ngroups && ok; ++g) ok = rows_of_group(g, kTilePix / ngroups) <= tp.rows_cap;
                 if (!ok) continue;
-                if (tid == 0) s_misc[3] = atomicAdd(tp.ovf_count + 3, 1);      // (header word 3: cleared by the ordering kernel)
+                if (tid == 0) s_misc[kMiscDrawn] = atomicAdd(tp.ovf_count + kTileHdrBwdEarly, 1);   // (cleared by the ordering kernel)
                 __syncthreads();
-                in_place = s_misc[3] < 32;
+                in_place = s_misc[kMiscDrawn] < 32;
                 break;
             }
             if (!in_place) {
@@ -989,7 +985,7 @@ __global__ __launch_bounds__(256, 2) void epipolar_bwd_tile_list_kernel(const Bw
     if constexpr (DET) {
         // The deterministic form: how many blocks share a tile depends on the tile alone -- kDetHardParts for the tiles listed from
         // the back (beyond this kernel's capacity: chains of group runs, started first), one for those listed from the front.
-        const int easy = tp.tile_count[0], hard = tp.tile_count[2] * kDetHardParts;
+        const int easy = tp.tile_count[kTileHdrCount], hard = tp.tile_count[kTileHdrDetHard] * kDetHardParts;
 #pragma unroll 1
         for (int idx = blockIdx.x; idx < hard + easy; idx += gridDim.x) {
             const bool h = idx < hard;

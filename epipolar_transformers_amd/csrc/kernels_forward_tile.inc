@@ -38,16 +38,8 @@ struct TileParams {
                             // tile then run as split-fp16 products (exact-fp32 redo of a tile whose rows overflow)
 };
 
-// the forward's array: rows of ROWS + 4 floats (16-byte aligned: the split second GEMM reads 16-byte fragments), and at
-// least the 2 x 32 x 528 bytes of fp16 stage of the split first GEMM
-constexpr int fwd_tile_array_floats(int rows) { return kTilePix * (rows + 4) > 8448 ? kTilePix * (rows + 4) : 8448; }
-// dynamic LDS of a block of ROWS = rows and KPL = kpl: what fwd_tile_body carves out of s_dyn -- the array, s_rows, s_pix,
-// s_misc[48], s_seg, bitmap + prefix of hw_words words each and, KPL == 1, the table of sample locations
-constexpr size_t fwd_tile_lds_bytes(int rows, int hw_words, int kpl)
-{
-    return (size_t)(fwd_tile_array_floats(rows) + rows + kTilePix + 48 + kTilePix * 4) * 4 + (size_t)hw_words * 8 +
-           (kpl == 1 ? (size_t)kTilePix * kWave * 8 : 0);
-}
+// dynamic LDS of a block of ROWS = rows and KPL = kpl: the layout fwd_tile_body takes its pointers from (et_tile_layout.h)
+constexpr size_t fwd_tile_lds_bytes(int rows, int hw_words, int kpl) { return (size_t)fwd_tile_lds(rows, hw_words, kpl).end; }
 
 // ---- the tile kernel -------------------------------------------------------------------------
 // C == 256 exactly.  Each wave owns 8 of the tile's 32 pixels for the K-long work (lanes <-> samples);
@@ -71,14 +63,17 @@ __device__ __forceinline__ void fwd_tile_body(const TileParams &tp, const int vb
     const int H = d.H, W = d.W, K = d.K;
     const int HW = H * W;
 
-    float *s_D = s_dyn;                                                  // [32][ROWS+4]  D, then B
-    int *s_rows = reinterpret_cast<int *>(s_D + fwd_tile_array_floats(ROWS)); // [ROWS] slot -> source pixel
-    int *s_pix = s_rows + kTileRowsMax;                                  // [32]  tile pixel ids
-    int *s_misc = s_pix + kTilePix;                                      // [4]   U ; [8..39] 1 / scale of the A rows (float)
-    float *s_seg = reinterpret_cast<float *>(s_misc + 48);               // [32][4] epipolar segments
-    unsigned *s_bitmap = reinterpret_cast<unsigned *>(s_seg + kTilePix * 4);  // [hw_words]
-    int *s_prefix = reinterpret_cast<int *>(s_bitmap + tp.hw_words);     // [hw_words] exclusive popcount prefix
-    f32x2 *s_nxy = reinterpret_cast<f32x2 *>(s_prefix + tp.hw_words);    // TAB: [32][64] normalised sample locations
+    const FwdTileLds L = fwd_tile_lds(ROWS, tp.hw_words, KPL);
+    char *const s_base = reinterpret_cast<char *>(s_dyn);
+    float *s_D = reinterpret_cast<float *>(s_base + L.arr);              // [32][ROWS+4]  D, then B
+    int *s_rows = reinterpret_cast<int *>(s_base + L.rows);              // [ROWS] slot -> source pixel
+    int *s_pix = reinterpret_cast<int *>(s_base + L.pix);                // [32]  tile pixel ids
+    int *s_U = reinterpret_cast<int *>(s_base + L.U);                    // rows of the tile's row set
+    float *s_ainv = reinterpret_cast<float *>(s_base + L.ainv);          // [32] 1 / scale of the A rows
+    float *s_seg = reinterpret_cast<float *>(s_base + L.seg);            // [32][4] epipolar segments
+    unsigned *s_bitmap = reinterpret_cast<unsigned *>(s_base + L.bitmap);  // [hw_words]
+    int *s_prefix = reinterpret_cast<int *>(s_base + L.prefix);          // [hw_words] exclusive popcount prefix
+    f32x2 *s_nxy = reinterpret_cast<f32x2 *>(s_base + L.nxy);            // TAB: [32][64] normalised sample locations
 
     const int n = vb / tp.tiles_per_pair;
     const int tile = vb - n * tp.tiles_per_pair;
@@ -208,10 +203,10 @@ __device__ __forceinline__ void fwd_tile_body(const TileParams &tp, const int vb
                 if (t < tp.hw_words) s_prefix[t] = carry + incl - c;
                 carry += __shfl(incl, kWave - 1);
             }
-            if (lane == 0) s_misc[0] = carry;
+            if (lane == 0) *s_U = carry;
         }
         __syncthreads();
-        const int U = s_misc[0];
+        const int U = *s_U;
         if (U > tp.rows_cap) {  // block-uniform: split the tile further
             return false;
         }
@@ -266,7 +261,7 @@ __device__ __forceinline__ void fwd_tile_body(const TileParams &tp, const int vb
             // a tile with a source value beyond fp16's range (checked on every converted value) is redone in exact fp32
             if (tp.scales && nb <= 8 * kPasses) {
                 const bool ovf = tile_gemm_rows_split<kTileStride, kPasses>(ref, src, stage_off, s_rows, s_D,
-                                                                            reinterpret_cast<float *>(s_misc + 8), U, nb, tid, wave,
+                                                                            s_ainv, U, nb, tid, wave,
                                                                             lane, tp.scales[n * 4 + 2], tp.scales[n * 4 + 3]);
                 split_ok = !__syncthreads_or(ovf);
                 __syncthreads();
@@ -577,7 +572,7 @@ __device__ __forceinline__ void fwd_tile_body(const TileParams &tp, const int vb
         }
     }
 
-    if (tp.stats && tid == 0 && part == 0) tp.stats[vb] = s_misc[0] | (ngroups << 16);
+    if (tp.stats && tid == 0 && part == 0) tp.stats[vb] = *s_U | (ngroups << 16);
 }
 
 // one block per tile, XCD-remapped so that an XCD walks whole pairs

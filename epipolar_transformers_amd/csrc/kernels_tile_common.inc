@@ -90,8 +90,7 @@ __device__ __forceinline__ void scatter_row(float *drow, const int (&sl)[4], con
 // When every wave has at most one pair of row blocks (nb <= 8) the A tile is first staged ONCE in LDS -- in the
 // D/B array itself, which is idle until the results are written -- and the waves read their A fragments from
 // there: the tile then pulls ~190 KB instead of ~290 KB from L2 in this phase.
-constexpr int kAStride = 260;  // floats per staged A row: 16-byte aligned rows, b128 fragment reads conflict-free
-constexpr int tile_array_floats(int rows) { return kTilePix * (rows + 1 > kAStride ? rows + 1 : kAStride); }
+// (kAStride floats per staged A row, tile_array_floats: et_tile_layout.h)
 
 // on_a_ready(staged): called once by every thread when the A tile can be read (staged = true: from LDS, row i at
 // s_D + i * kAStride), before any MFMA -- the forward copies its res_base rows there.

@@ -1,22 +1,11 @@
-// Included inside the anonymous namespace of a tile translation unit (et_tile_host.h does it): the shapes of the MFMA tile
-// path and the ORDERING of a tile call -- the sort key of every reference pixel's epipolar line, then one bitonic sort per
+// Included inside the anonymous namespace of a tile translation unit (et_tile_host.h does it): the ORDERING of a tile call (the shapes
+// of the MFMA tile path: et_tile_layout.h) -- the sort key of every reference pixel's epipolar line, then one bitonic sort per
 // pair in LDS -> perm (kernels_forward_tile.inc explains the tile formulation itself).
 //   tile_keys_kernel    per pixel, whole device: segment and sort key
 //   tile_order_kernel   one block per pair: sort -> perm, segments in tile order, base lines, scale estimates
 #pragma once
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kTilePix = 32;                    // reference pixels per tile (MFMA M)
-// Source rows a (sub)tile may touch = columns of the D/B array in LDS (template parameter ROWS of the kernel):
-// 256 for maps up to 64 x 64 (51.5 KB LDS, 3 blocks per CU), 384 for larger maps whose lines are longer
-// (68 KB, 2 blocks per CU; with 256 most tiles of a 96 x 96 map would overflow and split), 512 when one
-// pixel alone can touch more than 384 rows (K > 96 on maps above 96 x 96; 2 blocks per CU).  The array's
-// row stride is ROWS + 1: odd, so column reads are bank-conflict-free.
-constexpr int kTileRowsSmall = 256, kTileRowsLarge = 384, kTileRowsHuge = 512;
-// the warp-specialised persistent kernel above 64 x 64 (kernels_forward_tile_ws.inc, BT = true): 288-row arrays, maps up to
-// 96 x 96 (every tile of a 96 x 96 map has at most 280 rows; 384-row arrays do not fit its LDS)
-constexpr int kTileRowsWsLarge = 288, kWsMaxSideBand = 96, kWsMaxSideTwoPass = 128;
 
 // ---- ordering ------------------------------------------------------------------------------
 // The sort's keys in LDS: one spare slot after every 16 (a thread's 8 keys of a small-stride round are then 17 slots from its
@@ -81,9 +70,8 @@ __global__ __launch_bounds__(256) void tile_keys_kernel(const EtLayerDesc d, con
     const int HW = d.H * d.W;
     const int blocks_per_pair = (HW + (int)blockDim.x - 1) / (int)blockDim.x;
     const int n = blockIdx.x / blocks_per_pair, j = (blockIdx.x - n * blocks_per_pair) * blockDim.x + threadIdx.x;
-    // the forward's workspace header: [0] overflow-tile counter, [2..9] the per-XCD tile counters of the persistent kernel
-    // ([1] is the STICKY error word: never cleared here)
-    if (zero_word && blockIdx.x == 0 && threadIdx.x < 10 && threadIdx.x != 1) zero_word[threadIdx.x] = 0;
+    // the workspace header's counter words of both directions (et_tile_layout.h); the STICKY error word is never cleared here
+    if (zero_word && blockIdx.x == 0 && threadIdx.x < kTileHdrClearEnd && threadIdx.x != kTileHdrErr) zero_word[threadIdx.x] = 0;
     if (j >= HW) return;
     const float *cam = cam_all + (size_t)n * ET_CAM_STRIDE;
     const float cx = 0.5f * (d.xmin + d.xmax), cy = 0.5f * (d.ymin + d.ymax);

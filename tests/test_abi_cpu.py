@@ -186,10 +186,10 @@ def test_tile_path_eligibility_is_decided_on_the_host(lib):
                 int(lib.et_epipolar_backward_tiled_workspace_bytes(ctypes.byref(d))))
 
     def ws_bytes(tiles, pairs=3, hw=None):
-        # pixel order (32 per tile) | overflow counter + sticky error word (64 words) | overflow list | statistics | scales |
-        # segments
-        # (header of 64 words first: [0] overflow count, [1] sticky error word; one float4 base line per tile last)
-        # ... and the segments by pixel (tile_keys_kernel: the per-pixel half of the ordering), one float4 per pixel
+        # header of 64 words ([0] overflow count, [1] sticky error word) | pixel order (32 per tile) | overflow list |
+        # statistics | scales (4 per pair) | + 4: room to align what follows to 16 bytes | segments in tile order (one float4
+        # per pixel of a tile) | one float4 base line per tile | segments by pixel (tile_keys_kernel: the per-pixel half of
+        # the ordering), one float4 per pixel; + 256 bytes to align the base
         hw = (tiles // pairs) * 32 if hw is None else hw
         words = 64 + tiles * 32 + 2 * tiles + 4 * pairs + 4 + 4 * tiles * 32 + 4 * tiles + 4 * pairs * hw
         return words * 4 + 256
