@@ -29,6 +29,7 @@ UNITS = {
                              "et_tile_host.h", "et_tile_layout.h", "et_wave_reduce.h", "et_split_f16.h", "et_lds_layout.h"],
     "et_misc.hip": ["kernels_misc.inc"],
     "et_residual_gemm.hip": ["kernels_residual_gemm.inc", "et_wave_reduce.h"],
+    "et_triangulate.hip": ["et_triangulate.h", "et_wave_reduce.h"],
 }
 LIB = os.path.join(PKG, "lib", "libepipolar_amd.so")
 OBJ = os.path.join(PKG, "lib", "obj")

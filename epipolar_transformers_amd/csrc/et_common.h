@@ -22,6 +22,8 @@
 //                                                    kernels' LDS layouts (plain constexpr C++, also built by a host test)
 //   et_residual_gemm.hip  kernels_residual_gemm.inc  x = feat + bias + out . Wf^T as a split-fp16 GEMM, and the z branch's
 //                                                    batch statistics / backward (et_residual_gemm, et_z_*)
+//   et_triangulate.hip    et_triangulate.h           KEYPOINT.TRIANGULATION epipolar / epipolar_dlt: one wave per (frame, joint), a
+//                                                    lane per hypothesis, float64 Givens + Jacobi SVD; host + device routine
 //   et_misc.hip           kernels_misc.inc           sample_locs, residual epilogue, NCHW <-> NHWC, ABI version / errors
 //   et_wave_reduce.h                                 DPP wave reductions (wave_all_sum / max / min): general, tile, GEMM units
 //   et_split_f16.h                                   fp32 -> two fp16 halves for the matrix cores (tile units)

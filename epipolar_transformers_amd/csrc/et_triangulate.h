@@ -1,0 +1,336 @@
+// KEYPOINT.TRIANGULATION epipolar / epipolar_dlt (vision/triangulation.py:234-348) for ONE (frame, joint): the pieces the device
+// kernel and the host test hook share (plain C++, float64 throughout, __host__ __device__; included by et_triangulate.hip only).
+//
+//   select()               the confidence rule: views above float32(conf_thres), else the first arg-max; the branch
+//   solve_views()          DLT over a mask of views (+ the source view of a single one): rows x * P[2] - P[0], y * P[2] - P[1]
+//                          rotated ONE AT A TIME into a 4 x 4 upper-triangular R (Givens), then smallest_right_vector(R)
+//   evaluate_hypothesis()  hypothesis h = the h-th pair (a < b) of views: its two-view point and the selected views whose ray
+//                          passes within ransac_thres of it
+//   finish_hypothesis()    what the best hypothesis returns: nothing (no inlier), its own point, or the DLT over its inliers
+//
+// The kernel gives every lane one hypothesis and picks the winner with a wave arg-max; the host hook walks them in a loop.  Both
+// take the FIRST hypothesis with the largest count, so they agree.
+//
+// The SVD never forms A^T A (its condition number, ~1e5 here, would be squared): the rows go into R by Givens rotations, and a
+// one-sided Jacobi with a fixed number of sweeps orthogonalises R's four columns.  Every array below has compile-time indices
+// after unrolling: nothing is indexed by a run-time value, so nothing goes to scratch memory.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+namespace et_tri {
+
+constexpr int kMaxViews = 8;
+constexpr int kMaxPairs = kMaxViews * (kMaxViews - 1) / 2;   // 28 hypotheses at most: one wave holds them all
+constexpr int kJacobiSweeps = 12;                            // (a 4 x 4 converges in 4-6; the rest rotate by nothing)
+constexpr int kInfoNoInlier = 1 << 18;
+constexpr int kInfoClamped = 1 << 19;
+
+struct Problem {
+    int F, V, J, H, W;
+    const float *pts, *conf, *krt, *other_krt, *corr_pos;
+    double ds, resize, ransac_thres;
+    float conf_thres;   // float32(conf_thres): the reference compares its float32 scores with it IN float32
+    int dlt;
+    double *out;
+    int32_t *info;
+};
+
+struct Selection {
+    int mask;     // selected views
+    int branch;   // 0: two or more selected, 1: exactly one, 2: none (the first arg-max stands in)
+    int single;   // the one view of branches 1 and 2
+};
+
+struct Hypothesis {
+    int count;    // inliers (-1: this index names no pair of selected views)
+    int inliers;  // their mask
+    int pair;     // the two views of the hypothesis
+    double p[3];
+};
+
+#define ET_TRI_HD __host__ __device__ inline __attribute__((always_inline))
+
+ET_TRI_HD size_t view_row(const Problem &pr, int f, int v) { return (size_t)f * pr.V + v; }
+
+ET_TRI_HD Selection select(const Problem &pr, int f, int j)
+{
+    Selection s{0, 0, 0};
+    int n = 0, arg = 0;
+    float best = 0.f;
+    for (int v = 0; v < pr.V; ++v) {
+        const float c = pr.conf[view_row(pr, f, v) * pr.J + j];
+        if (c > pr.conf_thres) {
+            s.mask |= 1 << v;
+            s.single = v;
+            ++n;
+        }
+        if (v == 0 || c > best) {
+            best = c;
+            arg = v;
+        }
+    }
+    if (n == 0) {
+        s.mask = 1 << arg;
+        s.single = arg;
+        s.branch = 2;
+    } else if (n == 1) {
+        s.branch = 1;
+    }
+    return s;
+}
+
+// R <- the triangular factor of [R; row]
+ET_TRI_HD void rotate_row_in(double (&R)[4][4], double (&row)[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double a = R[k][k], b = row[k];
+        if (b != 0.0) {
+            const double h = sqrt(a * a + b * b);
+            const double c = a / h, s = b / h;
+#pragma unroll
+            for (int i = k; i < 4; ++i) {
+                const double t = c * R[k][i] + s * row[i];
+                row[i] = c * row[i] - s * R[k][i];
+                R[k][i] = t;
+            }
+        }
+    }
+}
+
+// the two DLT rows of an observation (x, y) under the projection P (12 floats)
+ET_TRI_HD void add_view(double (&R)[4][4], const float *P, double x, double y)
+{
+    double r0[4], r1[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        r0[i] = x * (double)P[8 + i] - (double)P[i];
+        r1[i] = y * (double)P[8 + i] - (double)P[4 + i];
+    }
+    rotate_row_in(R, r0);
+    rotate_row_in(R, r1);
+}
+
+// Right singular vector of R's smallest singular value, divided by its fourth component.  One-sided Jacobi: B = R V with V
+// orthogonal, columns of B rotated in pairs until they are orthogonal; their norms are then the singular values.
+ET_TRI_HD void smallest_right_vector(const double (&R)[4][4], double (&X)[3])
+{
+    double B[4][4], Vm[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            B[i][k] = k >= i ? R[i][k] : 0.0;
+            Vm[i][k] = i == k ? 1.0 : 0.0;
+        }
+#pragma unroll 1
+    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 4; ++q) {
+                double alpha = 0.0, beta = 0.0, gamma = 0.0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    alpha += B[i][p] * B[i][p];
+                    beta += B[i][q] * B[i][q];
+                    gamma += B[i][p] * B[i][q];
+                }
+                if (fabs(gamma) > 1e-17 * sqrt(alpha * beta)) {
+                    const double zeta = (beta - alpha) / (2.0 * gamma);
+                    const double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const double bp = B[i][p], bq = B[i][q];
+                        B[i][p] = c * bp - s * bq;
+                        B[i][q] = s * bp + c * bq;
+                        const double vp = Vm[i][p], vq = Vm[i][q];
+                        Vm[i][p] = c * vp - s * vq;
+                        Vm[i][q] = s * vp + c * vq;
+                    }
+                }
+            }
+    }
+    double least = 0.0, x[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        double n = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) n += B[i][k] * B[i][k];
+        if (k == 0 || n < least) {
+            least = n;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) x[i] = Vm[i][k];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) X[i] = x[i] / x[3];
+}
+
+// image coordinates of joint j in view v
+ET_TRI_HD void detection(const Problem &pr, int f, int v, int j, double &x, double &y)
+{
+    const float *p = pr.pts + (view_row(pr, f, v) * pr.J + j) * 2;
+    x = (double)p[0];
+    y = (double)p[1];
+}
+
+// DLT over the views of `mask` in ascending order
+ET_TRI_HD void solve_views(const Problem &pr, int f, int j, int mask, double (&X)[3])
+{
+    double R[4][4] = {};
+    for (int v = 0; v < pr.V; ++v)
+        if (mask >> v & 1) {
+            double x, y;
+            detection(pr, f, v, j, x, y);
+            add_view(R, pr.krt + view_row(pr, f, v) * 12, x, y);
+        }
+    smallest_right_vector(R, X);
+}
+
+// Branches 1 and 2: view v with the correspondence the layer found for the feature-map pixel under its detection.  Returns
+// kInfoClamped when that pixel lies outside the map (it is then clamped into it), else 0.
+ET_TRI_HD int solve_single(const Problem &pr, int f, int j, int v, double (&X)[3])
+{
+    double x, y;
+    detection(pr, f, v, j, x, y);
+    const double qx = (x / pr.resize + 0.5 - pr.ds / 2.0) / pr.ds;
+    const double qy = (y / pr.resize + 0.5 - pr.ds / 2.0) / pr.ds;
+    int ix, iy, flag = 0;
+    // int() truncates toward zero: (-1, 0) is pixel 0.  (The comparisons also send a NaN into the map.)
+    if (qx < (double)pr.W && qx > -1.0) ix = (int)qx;
+    else {
+        ix = qx < (double)pr.W ? 0 : pr.W - 1;
+        flag = kInfoClamped;
+    }
+    if (qy < (double)pr.H && qy > -1.0) iy = (int)qy;
+    else {
+        iy = qy < (double)pr.H ? 0 : pr.H - 1;
+        flag = kInfoClamped;
+    }
+    const float *c = pr.corr_pos + ((view_row(pr, f, v) * pr.H + iy) * pr.W + ix) * 2;
+    const double ox = ((double)c[0] * pr.ds + pr.ds / 2.0 - 0.5) * pr.resize;
+    const double oy = ((double)c[1] * pr.ds + pr.ds / 2.0 - 0.5) * pr.resize;
+    double R[4][4] = {};
+    add_view(R, pr.krt + view_row(pr, f, v) * 12, x, y);
+    add_view(R, pr.other_krt + view_row(pr, f, v) * 12, ox, oy);
+    smallest_right_vector(R, X);
+    return flag;
+}
+
+// distance of p from the ray of view v through its detection (point2line of triangulation.py:87-95)
+ET_TRI_HD double ray_distance(const Problem &pr, int f, int j, int v, const double (&p)[3])
+{
+    const float *M = pr.krt + view_row(pr, f, v) * 12;
+    const double a00 = M[0], a01 = M[1], a02 = M[2], a10 = M[4], a11 = M[5], a12 = M[6], a20 = M[8], a21 = M[9], a22 = M[10];
+    const double t[3] = {(double)M[3], (double)M[7], (double)M[11]};
+    double inv[3][3] = {{a11 * a22 - a12 * a21, a02 * a21 - a01 * a22, a01 * a12 - a02 * a11},
+                        {a12 * a20 - a10 * a22, a00 * a22 - a02 * a20, a02 * a10 - a00 * a12},
+                        {a10 * a21 - a11 * a20, a01 * a20 - a00 * a21, a00 * a11 - a01 * a10}};
+    const double det = a00 * inv[0][0] + a01 * inv[1][0] + a02 * inv[2][0];
+    double x, y;
+    detection(pr, f, v, j, x, y);
+    double c[3], x1[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) inv[i][k] /= det;
+        c[i] = -(inv[i][0] * t[0] + inv[i][1] * t[1] + inv[i][2] * t[2]);
+        x1[i] = (inv[i][0] * x + inv[i][1] * y + inv[i][2]) + c[i];
+    }
+    const double d1[3] = {x1[0] - p[0], x1[1] - p[1], x1[2] - p[2]};
+    const double d2[3] = {c[0] - p[0], c[1] - p[1], c[2] - p[2]};
+    const double d3[3] = {x1[0] - c[0], x1[1] - c[1], x1[2] - c[2]};
+    const double cr[3] = {d1[1] * d2[2] - d1[2] * d2[1], d1[2] * d2[0] - d1[0] * d2[2], d1[0] * d2[1] - d1[1] * d2[0]};
+    return sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]) / sqrt(d3[0] * d3[0] + d3[1] * d3[1] + d3[2] * d3[2]);
+}
+
+// Hypothesis h: the h-th pair a < b of ALL views in lexicographic order -- restricted to the selected views that is the
+// reference's enumeration without its mirrored (b, a) twins, which give the same point.
+ET_TRI_HD Hypothesis evaluate_hypothesis(const Problem &pr, int f, int j, int selected, int h)
+{
+    Hypothesis hy{-1, 0, 0, {0.0, 0.0, 0.0}};
+    int a = 0, b = 0, n = 0;
+    bool found = false;
+    for (int u = 0; u < pr.V; ++u)
+        for (int w = u + 1; w < pr.V; ++w)
+            if (n++ == h) {
+                a = u;
+                b = w;
+                found = true;
+            }
+    hy.pair = (1 << a) | (1 << b);
+    if (!found || (selected & hy.pair) != hy.pair) return hy;
+    solve_views(pr, f, j, hy.pair, hy.p);
+    hy.count = 0;
+    for (int v = 0; v < pr.V; ++v)
+        if ((selected >> v & 1) && ray_distance(pr, f, j, v, hy.p) < pr.ransac_thres) {
+            ++hy.count;
+            hy.inliers |= 1 << v;
+        }
+    return hy;
+}
+
+// What the best hypothesis returns; the bits 8.. of the info word.
+ET_TRI_HD int finish_hypothesis(const Problem &pr, int f, int j, const Hypothesis &best, double (&X)[3])
+{
+    if (best.count <= 0) {
+        X[0] = X[1] = X[2] = 0.0;
+        return kInfoNoInlier;
+    }
+    if (best.count > 2) {
+        solve_views(pr, f, j, best.inliers, X);
+        return best.inliers << 8;
+    }
+    X[0] = best.p[0];
+    X[1] = best.p[1];
+    X[2] = best.p[2];
+    return best.pair << 8;
+}
+
+ET_TRI_HD void store(const Problem &pr, int f, int j, const double (&X)[3], int info)
+{
+    double *o = pr.out + ((size_t)f * pr.J + j) * 3;
+    o[0] = X[0];
+    o[1] = X[1];
+    o[2] = X[2];
+    if (pr.info) pr.info[(size_t)f * pr.J + j] = info;
+}
+
+// The joints that need no hypothesis search: one view and its correspondence, or epipolar_dlt.  Returns false for the others.
+ET_TRI_HD bool solve_direct(const Problem &pr, int f, int j, const Selection &s)
+{
+    double X[3];
+    if (s.branch != 0) {
+        const int flag = solve_single(pr, f, j, s.single, X);
+        store(pr, f, j, X, s.mask | s.mask << 8 | s.branch << 16 | flag);
+        return true;
+    }
+    if (pr.dlt) {
+        solve_views(pr, f, j, s.mask, X);
+        store(pr, f, j, X, s.mask | s.mask << 8);
+        return true;
+    }
+    return false;
+}
+
+// the whole joint, hypotheses one after the other (the host hook)
+inline void joint_serial(const Problem &pr, int f, int j)
+{
+    const Selection s = select(pr, f, j);
+    if (solve_direct(pr, f, j, s)) return;
+    Hypothesis best{-1, 0, 0, {0.0, 0.0, 0.0}};
+    for (int h = 0; h < pr.V * (pr.V - 1) / 2; ++h) {
+        const Hypothesis hy = evaluate_hypothesis(pr, f, j, s.mask, h);
+        if (hy.count > best.count) best = hy;
+    }
+    double X[3];
+    const int bits = finish_hypothesis(pr, f, j, best, X);
+    store(pr, f, j, X, s.mask | bits);
+}
+
+#undef ET_TRI_HD
+
+}  // namespace et_tri

@@ -1,0 +1,77 @@
+// libepipolar_amd.so: KEYPOINT.TRIANGULATION epipolar / epipolar_dlt -- the lifting that consumes the layer's corr_pos
+// (vision/triangulation.py:234-348).  One wave per (frame, joint), four waves per block, one lane per hypothesis; float64.
+// No atomics, no LDS: the result is bit-reproducible from run to run.
+#include "et_common.h"
+#include "et_triangulate.h"
+
+namespace {
+#include "et_wave_reduce.h"
+
+__global__ __launch_bounds__(kWave * kWavesPerBlock) void triangulate_epipolar_kernel(const et_tri::Problem pr)
+{
+    const int lane = threadIdx.x & (kWave - 1);
+    const long long item = (long long)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    if (item >= (long long)pr.F * pr.J) return;      // (whole waves leave: the reductions below see 64 lanes)
+    const int f = (int)(item / pr.J), j = (int)(item % pr.J);
+    const et_tri::Selection s = et_tri::select(pr, f, j);
+    if (s.branch != 0 || pr.dlt) {                    // wave-uniform: one solve, no search
+        if (lane == 0) et_tri::solve_direct(pr, f, j, s);
+        return;
+    }
+    const et_tri::Hypothesis hy = et_tri::evaluate_hypothesis(pr, f, j, s.mask, lane);
+    // arg-max keyed on (count, -hypothesis index): the first hypothesis with the largest count.  Exact in float (<= 8 * 64 + 63),
+    // and unique to its lane, so exactly one lane finds its own key back.
+    const float key = hy.count >= 0 ? (float)(hy.count * kWave + (kWave - 1 - lane)) : -1.f;
+    if (key == wave_all_max(key)) {
+        double X[3];
+        const int bits = et_tri::finish_hypothesis(pr, f, j, hy, X);
+        et_tri::store(pr, f, j, X, s.mask | bits);
+    }
+}
+
+int make_problem(const char *what, int32_t F, int32_t V, int32_t J, int32_t H, int32_t W, const float *pts, const float *conf,
+                 const float *krt, const float *other_krt, const float *corr_pos, float downsample, float resize,
+                 double conf_thres, double ransac_thres, int32_t dlt, double *out, int32_t *info, et_tri::Problem *pr)
+{
+    if (F < 1 || J < 1 || (long long)F * J > 0x7fffffffLL - kWavesPerBlock) return fail("%s: bad sizes F=%d J=%d", what, F, J);
+    if (V < 1 || V > et_tri::kMaxViews) return fail("%s: V=%d outside [1, %d]", what, V, et_tri::kMaxViews);
+    if (H < 1 || W < 1) return fail("%s: bad map size H=%d W=%d", what, H, W);
+    if (!pts || !conf || !krt || !other_krt || !corr_pos || !out) return fail("%s: NULL pointer", what);
+    if (!(downsample > 0.f) || !(resize > 0.f)) return fail("%s: downsample / resize must be positive", what);
+    *pr = et_tri::Problem{F, V, J, H, W, pts, conf, krt, other_krt, corr_pos, (double)downsample, (double)resize, ransac_thres,
+                          (float)conf_thres, dlt != 0, out, info};
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int et_triangulate_epipolar(int32_t F, int32_t V, int32_t J, int32_t H, int32_t W, const float *pts, const float *conf,
+                            const float *krt, const float *other_krt, const float *corr_pos, float downsample, float resize,
+                            double conf_thres, double ransac_thres, int32_t dlt, double *out, int32_t *info, void *stream)
+{
+    et_tri::Problem pr;
+    if (int e = make_problem("et_triangulate_epipolar", F, V, J, H, W, pts, conf, krt, other_krt, corr_pos, downsample, resize,
+                             conf_thres, ransac_thres, dlt, out, info, &pr))
+        return e;
+    const unsigned blocks = (unsigned)(((long long)F * J + kWavesPerBlock - 1) / kWavesPerBlock);
+    hipLaunchKernelGGL(triangulate_epipolar_kernel, dim3(blocks), dim3(kWave * kWavesPerBlock), 0, (hipStream_t)stream, pr);
+    return check_launch("et_triangulate_epipolar");
+}
+
+int et_debug_host_triangulate_epipolar(int32_t F, int32_t V, int32_t J, int32_t H, int32_t W, const float *pts, const float *conf,
+                                       const float *krt, const float *other_krt, const float *corr_pos, float downsample,
+                                       float resize, double conf_thres, double ransac_thres, int32_t dlt, double *out,
+                                       int32_t *info)
+{
+    et_tri::Problem pr;
+    if (int e = make_problem("et_debug_host_triangulate_epipolar", F, V, J, H, W, pts, conf, krt, other_krt, corr_pos, downsample,
+                             resize, conf_thres, ransac_thres, dlt, out, info, &pr))
+        return e;
+    for (int f = 0; f < F; ++f)
+        for (int j = 0; j < J; ++j) et_tri::joint_serial(pr, f, j);
+    return 0;
+}
+
+}  // extern "C"

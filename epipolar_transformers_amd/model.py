@@ -10,7 +10,9 @@ What changes against the reference:
     samples share a BN batch).  MERGE late -- the headline mode; early / both fuse layer1 features with the source's
     DECONVOLUTION features (resnet.py:390-396), which needs the unfused pass first, so they keep two passes.
   * N3 -- test-time lifting stays on the GPU: batched float64 SVD-DLT (`triangulate.py`) instead of the per-joint
-    pymvg loop on the CPU (vision/triangulation.py:400-441), no device-to-host copy of the detections.
+    pymvg loop on the CPU (vision/triangulation.py:400-441), no device-to-host copy of the detections; with
+    KEYPOINT.TRIANGULATION epipolar / epipolar_dlt the reference's `triangulate_epipolar` (:234-348), which consumes the
+    layer's corr_pos, as one HIP kernel (`ops.triangulate_epipolar`).
   * `EPIPOLAR.MULTITEST` (model.py:213-239): every other view in turn as the source, per joint the detection with
     the highest score -- here all (reference, source) combinations go through ONE launch of the fused layer.
   * `BACKBONE.SYNC_BN` converts through `parallel.convert_sync_batchnorm` (model.py:56-58).
@@ -23,7 +25,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from . import backbones
+from . import backbones, ops
 from .config import get_cfg
 from .triangulate import mpjpe, triangulate_dlt
 
@@ -154,14 +156,33 @@ class MultiViewPoseModel(nn.Module):
         return locs, best
 
     # ------------------------------------------------------------------------------------------ N3
-    def lift(self, batch_locs: torch.Tensor, batch_scos: torch.Tensor, KRT: torch.Tensor, num_views: int):
-        """(F*V, J, 2) detections -> (F, J, 3) world points: the 'naive' / 'pymvg' linear triangulation of
-        model.py:281-302, on the device the detections live on."""
+    def lift(self, batch_locs: torch.Tensor, batch_scos: torch.Tensor, KRT: torch.Tensor, num_views: int,
+             corr_pos: torch.Tensor = None, other_KRT: torch.Tensor = None):
+        """(F*V, J, 2) detections -> (F, J, 3) world points, on the device the detections live on, by the method
+        cfg.KEYPOINT.TRIANGULATION names (model.py:295-311):
+          epipolar / epipolar_dlt   triangulate_epipolar (vision/triangulation.py:234-348) as one HIP kernel
+                                    (ops.triangulate_epipolar); needs the layer's corr_pos (F*V,H,W,2) and the projections of
+                                    the source views other_KRT (F*V,3,4), with KEYPOINT.CONF_THRES / RANSAC_THRES;
+          anything else             the thresholded linear DLT of triangulate.py (the reference's `pymvg`; its always-random
+                                    `naive` / `refine` and `rpsm` are not restated and take this path too)."""
         cfg = self.cfg
         m, j, _ = batch_locs.shape
         f = m // num_views
         scale = float(cfg.DATASETS.IMAGE_RESIZE) * float(cfg.DATASETS.PREDICT_RESIZE)
         pts = (batch_locs * scale).view(f, num_views, j, 2)
+        method = getattr(cfg.KEYPOINT, "TRIANGULATION", "naive")
+        if method in ("epipolar", "epipolar_dlt"):
+            if corr_pos is None or other_KRT is None:
+                raise ValueError("KEYPOINT.TRIANGULATION %s needs the layer's corr_pos and the source views' projections; "
+                                 "EPIPOLAR.MULTITEST keeps neither (every other view is the source in turn): use pymvg with it"
+                                 % method)
+            dev = batch_locs.device
+            planes = lambda t: t.to(dev, torch.float32).reshape(f, num_views, 3, 4).contiguous()
+            return ops.triangulate_epipolar(
+                pts.contiguous(), batch_scos.reshape(f, num_views, j).contiguous(), planes(KRT), planes(other_KRT),
+                corr_pos.reshape(f, num_views, *corr_pos.shape[-3:]).contiguous(), downsample=float(cfg.BACKBONE.DOWNSAMPLE),
+                resize=scale, conf_thres=float(getattr(cfg.KEYPOINT, "CONF_THRES", 0.05)),
+                ransac_thres=float(getattr(cfg.KEYPOINT, "RANSAC_THRES", 3)), dlt=method == "epipolar_dlt")
         return triangulate_dlt(pts, KRT.to(batch_locs.device).view(f, num_views, 3, 4), batch_scos.view(f, num_views, j),
                                conf_thres=float(getattr(cfg.KEYPOINT, "CONF_THRES", 0.05)))
 
@@ -180,18 +201,19 @@ class MultiViewPoseModel(nn.Module):
         if cfg.EPIPOLAR.MULTITEST and not is_train:
             with torch.no_grad():
                 batch_locs, batch_scos = self.forward_multitest(img, KRT, views)
-            heat = corr_pos = depths = None
+            heat = corr_pos = depths = other_KRT = None
         else:
             if self.sharded is not None and "other_img" not in inputs and "other_index" not in inputs:
-                res = self.forward_views_sharded(img, KRT, inputs["other_KRT"].to(torch.float32), camera, other_camera,
-                                                 int(inputs.get("exchange_chunks", 1)))
+                other_KRT = inputs["other_KRT"].to(torch.float32)
+                res = self.forward_views_sharded(img, KRT, other_KRT, camera, other_camera, int(inputs.get("exchange_chunks", 1)))
             elif "other_index" in inputs:
+                other_KRT = KRT[inputs["other_index"].to(KRT.device)]
                 res = self.forward_views(img, KRT, inputs["other_index"], camera, other_camera)
             else:
+                other_KRT = inputs["other_KRT"].to(torch.float32)
                 with torch.set_grad_enabled(torch.is_grad_enabled() and bool(cfg.EPIPOLAR.OTHER_GRAD)):
                     other_features = self.backbone(inputs["other_img"])[0]                           # model.py:244
-                res = self.reference(img, [other_features, inputs["other_KRT"].to(torch.float32), None, KRT, camera,
-                                           other_camera, inputs["other_img"]])                       # model.py:246
+                res = self.reference(img, [other_features, other_KRT, None, KRT, camera, other_camera, inputs["other_img"]])  # model.py:246
             _, heat, batch_locs, batch_scos, corr_pos, depths, _, _ = res
         loss_dict, metric_dict, out = {}, {}, {}
         if is_train and inputs.get("heatmap") is not None:
@@ -203,7 +225,7 @@ class MultiViewPoseModel(nn.Module):
                    batch_locs=batch_locs, score_pred=batch_scos, batch_scos=batch_scos,
                    heatmaps=heat[0] if heat is not None else None)
         if not is_train and cfg.VIS.MULTIVIEW:
-            pred = self.lift(batch_locs, batch_scos, KRT, views)
+            pred = self.lift(batch_locs, batch_scos, KRT, views, corr_pos, other_KRT)
             out["points-3d"] = pred
             if inputs.get("points-3d") is not None:
                 gt = inputs["points-3d"].to(pred.device).view(-1, views, pred.shape[1], 3)[:, 0]

@@ -813,6 +813,42 @@ def heatmap_peaks(heatmaps: torch.Tensor, radius: float, downsample: float, thre
     return locs, scores
 
 
+def triangulate_epipolar(pts: torch.Tensor, conf: torch.Tensor, krt: torch.Tensor, other_krt: torch.Tensor,
+                         corr_pos: torch.Tensor, *, downsample: float, resize: float, conf_thres: float, ransac_thres: float,
+                         dlt: bool = False, want_info: bool = False):
+    """KEYPOINT.TRIANGULATION epipolar (`dlt` False) / epipolar_dlt (True): triangulate_epipolar of
+    vision/triangulation.py:234-348 for all frames and joints in ONE kernel (et_triangulate_epipolar, float64 arithmetic).
+    pts (F,V,J,2): image coordinates already multiplied by `resize` = IMAGE_RESIZE * PREDICT_RESIZE; conf (F,V,J); krt,
+    other_krt (F,V,3,4): every view's projection and its source view's; corr_pos (F,V,H,W,2): the layer's correspondences
+    for the frame-major batch.  Returns the (F,J,3) float64 world points -- and, with `want_info`, the (F,J) int32 decision
+    word of include/epipolar_amd.h (selected views, views used, branch, no-inlier and clamp flags).
+
+    Two deviations from the reference.  The pair hypotheses are always enumerated: the reference draws 100 random pairs when
+    J >= 10 (triangulation.py:303, 322-340), which for V <= 8 is the same hypothesis set in an order that only decides ties;
+    this is its own J < 10 branch, deterministic.  A detection whose feature-map pixel lies outside corr_pos is clamped into
+    the map and flagged (info bit 19); the reference wraps a negative index and raises on a large one.  No gradient."""
+    _require_gpu(pts, "pts")
+    if pts.dim() != 4 or pts.shape[-1] != 2:
+        raise ValueError("pts must be (F,V,J,2), got %s" % (tuple(pts.shape),))
+    f, v, j, _ = pts.shape
+    dev = pts.device
+    _require_f32(pts, "pts", dev)
+    _require_f32(conf, "conf", dev, (f, v, j))
+    _require_f32(krt, "krt", dev, (f, v, 3, 4))
+    _require_f32(other_krt, "other_krt", dev, (f, v, 3, 4))
+    _require_gpu(corr_pos, "corr_pos")
+    if corr_pos.dim() != 5:
+        raise ValueError("corr_pos must be (F,V,H,W,2) = (%d,%d,H,W,2), got %s" % (f, v, tuple(corr_pos.shape)))
+    h, w = corr_pos.shape[2:4]
+    _require_f32(corr_pos, "corr_pos", dev, (f, v, h, w, 2))
+    out = _empty((f, j, 3), device=dev, dtype=torch.float64)
+    info = torch.empty((f, j), dtype=torch.int32, device=dev) if want_info else None
+    _call("et_triangulate_epipolar", pts, f, v, j, h, w, _ptr(pts), _ptr(conf), _ptr(krt), _ptr(other_krt), _ptr(corr_pos),
+          float(downsample), float(resize), float(conf_thres), float(ransac_thres), int(bool(dlt)), _ptr(out), _ptr(info),
+          _stream(pts))
+    return (out, info) if want_info else out
+
+
 class EpipolarAttend(torch.autograd.Function):
     """out = sum_k softmax_k(scale * mask(f_ref . S_k)) S_k with S_k the K bilinear
     samples of f_src on the pixel's epipolar segment (epipolar.py:188-247).

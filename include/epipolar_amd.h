@@ -426,6 +426,38 @@ int et_epipolar_forward_fused(const EtLayerDesc *desc, const float *xs, const fl
 int et_heatmap_peaks(int64_t num_maps, int32_t H, int32_t W, const float *heatmaps, float radius, float downsample,
                      float threshold, int32_t legacy_floor_division, float *locs, float *scores, void *stream);
 
+/* KEYPOINT.TRIANGULATION epipolar / epipolar_dlt: triangulate_epipolar (vision/triangulation.py:234-348), the lifting that
+ * consumes the layer's corr_pos.  Every (frame, joint) is independent; inputs float32, all arithmetic float64.  One launch.
+ *   pts       : (F, V, J, 2) image coordinates, already multiplied by resize = IMAGE_RESIZE * PREDICT_RESIZE
+ *   conf      : (F, V, J) ;  krt : (F, V, 3, 4) ;  other_krt : (F, V, 3, 4) the projection of each view's source view
+ *   corr_pos  : (F, V, H, W, 2) feature-map pixels, [..., 0] = x: the layer's output for the frame-major batch
+ *   downsample: cfg.BACKBONE.DOWNSAMPLE ;  conf_thres / ransac_thres : cfg.KEYPOINT.CONF_THRES / RANSAC_THRES
+ *   dlt       : 0 = epipolar, else epipolar_dlt
+ *   out       : (F, J, 3) float64 world points ;  info : (F, J) int32 or NULL
+ * A view is selected when conf > float32(conf_thres), compared in float32.  None selected: the first arg-max of conf alone
+ * (branch 2); one selected: branch 1; both triangulate that view's detection against its corr_pos entry in the source view
+ * (DLT of the two views' rows).  Two or more (branch 0): with dlt, the DLT over the selected views; otherwise every pair a < b
+ * of selected views is a hypothesis (its two-view DLT point p), its inliers are the selected views whose ray through their
+ * detection passes p closer than ransac_thres, and the FIRST hypothesis with the largest inlier count wins: more than two
+ * inliers -> the DLT over them, one or two -> p, none -> (0, 0, 0).
+ * Two deviations from the reference: the hypotheses are always enumerated (the reference samples 100 random pairs when
+ * J >= 10: the same set for V <= 8, in an order that only decides ties), and a corr_pos index outside the map is clamped into
+ * it and flagged (the reference wraps a negative index and raises on a large one).
+ *   info bits 0-7  : selected views           bits 8-15 : the views the returned point was computed from (none: 0)
+ *        bits 16-17: branch                   bit 18    : no hypothesis had an inlier       bit 19 : the lookup was clamped
+ * V <= 8.  No atomics: bit-reproducible. */
+int et_triangulate_epipolar(int32_t F, int32_t V, int32_t J, int32_t H, int32_t W, const float *pts, const float *conf,
+                            const float *krt, const float *other_krt, const float *corr_pos, float downsample, float resize,
+                            double conf_thres, double ransac_thres, int32_t dlt, double *out, int32_t *info, void *stream);
+
+/* Test hook (HOST pointers, runs on the CPU, no GPU needed): the per-joint routine of et_triangulate_epipolar
+ * (csrc/et_triangulate.h, shared with the kernel) in a serial loop over frames, joints and hypotheses.  Not a CPU fallback of
+ * the path. */
+int et_debug_host_triangulate_epipolar(int32_t F, int32_t V, int32_t J, int32_t H, int32_t W, const float *pts, const float *conf,
+                                       const float *krt, const float *other_krt, const float *corr_pos, float downsample,
+                                       float resize, double conf_thres, double ransac_thres, int32_t dlt, double *out,
+                                       int32_t *info);
+
 /* Layout converters between the reference's NCHW and the kernels' NHWC. */
 int et_nchw_to_nhwc(int32_t N, int32_t C, int32_t H, int32_t W, const float *src, float *dst, void *stream);
 int et_nhwc_to_nchw(int32_t N, int32_t C, int32_t H, int32_t W, const float *src, float *dst, void *stream);
