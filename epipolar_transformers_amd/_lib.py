@@ -14,16 +14,6 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EPIPOLAR_AMD_LIB") or os.path.join(_PKG, "lib", "libepipolar_amd.so")
 
 ET_CAM_STRIDE = 27
-ET_VARIANT_SAFE_REDUCE = 1
-ET_VARIANT_NO_TAP_CACHE = 2
-ET_VARIANT_PIXEL_INTERLEAVE = 4
-ET_VARIANT_BATCH4 = 8
-ET_VARIANT_OCC5 = 16
-ET_VARIANT_OCC6 = 32
-ET_VARIANT_BASELINE = 256
-ET_VARIANT_PIPELINE = 512
-ET_VARIANT_MULTI2 = 1024
-ET_VARIANT_MULTI4 = 2048
 ET_VARIANT_BWD_ATOMIC = 4096
 ET_VARIANT_BWD_UNSORTED = 8192
 ET_VARIANT_NO_TILE = 16384

@@ -6,13 +6,20 @@ namespace {
 #include "kernels_pixel_phases.inc"
 #include "kernels_backward.inc"  // epipolar_bwd_kernel, epipolar_bwd_emit_kernel, bwd_scan/bucket, epipolar_bwd_gather_kernel
 
-template <int CPD, int KPL>
-void launch_bwd(const BwdParams &p, int variant, dim3 grid, hipStream_t st)
+template <int CPD>
+void launch_bwd(const BwdParams &p, int kpl, dim3 grid, hipStream_t st)
 {
-    if (variant & ET_VARIANT_SAFE_REDUCE)
-        hipLaunchKernelGGL((epipolar_bwd_kernel<CPD, KPL, false>), grid, dim3(256), 0, st, p);
-    else
-        hipLaunchKernelGGL((epipolar_bwd_kernel<CPD, KPL, true>), grid, dim3(256), 0, st, p);
+    if (kpl == 1) hipLaunchKernelGGL((epipolar_bwd_kernel<CPD, 1>), grid, dim3(256), 0, st, p);
+    else if (kpl == 2) hipLaunchKernelGGL((epipolar_bwd_kernel<CPD, 2>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((epipolar_bwd_kernel<CPD, 4>), grid, dim3(256), 0, st, p);
+}
+
+template <int CPL>
+void launch_emit(const BwdParams &p, int kpl, dim3 grid, size_t lds, hipStream_t st)
+{
+    if (kpl == 1) hipLaunchKernelGGL((epipolar_bwd_emit_kernel<CPL, 1>), grid, dim3(256), lds, st, p);
+    else if (kpl == 2) hipLaunchKernelGGL((epipolar_bwd_emit_kernel<CPL, 2>), grid, dim3(256), lds, st, p);
+    else hipLaunchKernelGGL((epipolar_bwd_emit_kernel<CPL, 4>), grid, dim3(256), lds, st, p);
 }
 }  // namespace
 
@@ -86,29 +93,14 @@ int et_epipolar_backward_ga(const EtLayerDesc *desc, const float *xs, const floa
     }
     const dim3 grid((unsigned)total);
     const int cpd = (desc->C + 63) / 64, kpl = (desc->K + 63) / 64;
-    const int v = desc->variant;
     if (gather) {
         const size_t lds_e = (size_t)kWavesPerBlock * (kpl * kWave * 16 + 3 * p.cap * 4);
-        const bool safe = v & ET_VARIANT_SAFE_REDUCE;
-#define ET_EMIT(CPLv, KPLv)                                                                                        \
-    do {                                                                                                           \
-        if (safe) hipLaunchKernelGGL((epipolar_bwd_emit_kernel<CPLv, KPLv, false>), grid, dim3(256), lds_e, st, p); \
-        else hipLaunchKernelGGL((epipolar_bwd_emit_kernel<CPLv, KPLv, true>), grid, dim3(256), lds_e, st, p);       \
-    } while (0)
-        if (desc->C <= 256) { if (kpl == 1) ET_EMIT(1, 1); else if (kpl == 2) ET_EMIT(1, 2); else ET_EMIT(1, 4); }
-        else { if (kpl == 1) ET_EMIT(2, 1); else if (kpl == 2) ET_EMIT(2, 2); else ET_EMIT(2, 4); }
-#undef ET_EMIT
-    } else {
-#define ET_BWD_CASE(CPD)                                   \
-    if (kpl == 1) launch_bwd<CPD, 1>(p, v, grid, st);      \
-    else if (kpl == 2) launch_bwd<CPD, 2>(p, v, grid, st); \
-    else launch_bwd<CPD, 4>(p, v, grid, st);
-    if (cpd <= 1) { ET_BWD_CASE(1) }
-    else if (cpd <= 2) { ET_BWD_CASE(2) }
-    else if (cpd <= 4) { ET_BWD_CASE(4) }
-    else { ET_BWD_CASE(8) }
-#undef ET_BWD_CASE
-    }
+        if (desc->C <= 256) launch_emit<1>(p, kpl, grid, lds_e, st);
+        else launch_emit<2>(p, kpl, grid, lds_e, st);
+    } else if (cpd <= 1) launch_bwd<1>(p, kpl, grid, st);
+    else if (cpd <= 2) launch_bwd<2>(p, kpl, grid, st);
+    else if (cpd <= 4) launch_bwd<4>(p, kpl, grid, st);
+    else launch_bwd<8>(p, kpl, grid, st);
     if (int e = check_launch("et_epipolar_backward")) return e;
     if (gather) {
         hipLaunchKernelGGL(bwd_scan_kernel, dim3(desc->N), dim3(256), 0, st, HW, p.row_count, row_base, row_cursor);

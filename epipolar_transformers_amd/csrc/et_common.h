@@ -95,8 +95,6 @@ struct FwdParams {
     float *res_base;
     int blocks_per_pair;
     int total_blocks;
-    int interleave;
-    int ablate;  // profiling only: 1 = issue no tap loads after the first sample, 2 = every tap reads row 0
 };
 
 struct BwdParams {
@@ -140,114 +138,65 @@ __device__ __forceinline__ float dpp(float v)
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
 }
 
-// Lanes whose `bit` is clear keep a, the others keep b; each adds the value its
-// partner (lane ^ bit) did not keep.  Building block of the transposing sum.
-__device__ __forceinline__ float xstep_safe(float a, float b, int lane, int bit)
-{
-    const bool hi = (lane & bit) != 0;
-    const float keep = hi ? b : a;
-    const float send = hi ? a : b;
-    return keep + __shfl_xor(send, bit);
-}
-
 // Sum eight per-lane partials over the 64 lanes at once.  Result: the 8-lane
 // group g = lane >> 3 holds (replicated) the total of partial j = bitrev3(g),
 // i.e. j = ((lane >> 5) & 1) | ((lane >> 4) & 1) << 1 | ((lane >> 3) & 1) << 2.
-template <bool FAST>
 __device__ __forceinline__ float reduce8(const float (&p)[8], int lane)
 {
-    if constexpr (FAST) {
-        float q[4];
+    float q[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            // v_permlane32_swap: a' = [a.lo, b.lo], b' = [a.hi, b.hi]
-            auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(p[2 * i]), __float_as_uint(p[2 * i + 1]),
-                                                      false, false);
-            q[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-        }
-        float t[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            // v_permlane16_swap: odd rows of a <-> even rows of b
-            auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(q[2 * i]), __float_as_uint(q[2 * i + 1]),
-                                                      false, false);
-            t[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-        }
-        const bool hi = (lane & 8) != 0;
-        const float keep = hi ? t[1] : t[0];
-        const float send = hi ? t[0] : t[1];
-        float u = keep + dpp<0x128>(send);  // row_ror:8  == lane ^ 8 inside a row of 16
-        u += dpp<0xB1>(u);                  // quad_perm [1,0,3,2]  (lane ^ 1)
-        u += dpp<0x4E>(u);                  // quad_perm [2,3,0,1]  (lane ^ 2)
-        u += dpp<0x141>(u);                 // row_half_mirror      (7 - lane inside 8)
-        return u;
-    } else {
-        const float q0 = xstep_safe(p[0], p[1], lane, 32);
-        const float q1 = xstep_safe(p[2], p[3], lane, 32);
-        const float q2 = xstep_safe(p[4], p[5], lane, 32);
-        const float q3 = xstep_safe(p[6], p[7], lane, 32);
-        const float t0 = xstep_safe(q0, q1, lane, 16);
-        const float t1 = xstep_safe(q2, q3, lane, 16);
-        float u = xstep_safe(t0, t1, lane, 8);
-        u += __shfl_xor(u, 4);
-        u += __shfl_xor(u, 2);
-        u += __shfl_xor(u, 1);
-        return u;
+    for (int i = 0; i < 4; ++i) {
+        // v_permlane32_swap: a' = [a.lo, b.lo], b' = [a.hi, b.hi]
+        auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(p[2 * i]), __float_as_uint(p[2 * i + 1]), false, false);
+        q[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
     }
+    float t[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        // v_permlane16_swap: odd rows of a <-> even rows of b
+        auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(q[2 * i]), __float_as_uint(q[2 * i + 1]), false, false);
+        t[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    }
+    const bool hi = (lane & 8) != 0;
+    const float keep = hi ? t[1] : t[0];
+    const float send = hi ? t[0] : t[1];
+    float u = keep + dpp<0x128>(send);  // row_ror:8  == lane ^ 8 inside a row of 16
+    u += dpp<0xB1>(u);                  // quad_perm [1,0,3,2]  (lane ^ 1)
+    u += dpp<0x4E>(u);                  // quad_perm [2,3,0,1]  (lane ^ 2)
+    u += dpp<0x141>(u);                 // row_half_mirror      (7 - lane inside 8)
+    return u;
 }
 
 // Four-partial variant: the 16-lane row r = lane >> 4 holds the total of partial
 // j = ((lane >> 5) & 1) | ((lane >> 4) & 1) << 1.
-template <bool FAST>
 __device__ __forceinline__ float reduce4(const float (&p)[4], int lane)
 {
-    if constexpr (FAST) {
-        float q[2];
+    float q[2];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(p[2 * i]), __float_as_uint(p[2 * i + 1]),
-                                                      false, false);
-            q[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-        }
-        auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(q[0]), __float_as_uint(q[1]), false, false);
-        float u = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-        u += dpp<0x128>(u);  // row_ror:8
-        u += dpp<0x124>(u);  // row_ror:4
-        u += dpp<0x122>(u);  // row_ror:2
-        u += dpp<0x121>(u);  // row_ror:1
-        return u;
-    } else {
-        const float q0 = xstep_safe(p[0], p[1], lane, 32);
-        const float q1 = xstep_safe(p[2], p[3], lane, 32);
-        float u = xstep_safe(q0, q1, lane, 16);
-        u += __shfl_xor(u, 8);
-        u += __shfl_xor(u, 4);
-        u += __shfl_xor(u, 2);
-        u += __shfl_xor(u, 1);
-        return u;
+    for (int i = 0; i < 2; ++i) {
+        auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(p[2 * i]), __float_as_uint(p[2 * i + 1]), false, false);
+        q[i] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
     }
+    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(q[0]), __float_as_uint(q[1]), false, false);
+    float u = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    u += dpp<0x128>(u);  // row_ror:8
+    u += dpp<0x124>(u);  // row_ror:4
+    u += dpp<0x122>(u);  // row_ror:2
+    u += dpp<0x121>(u);  // row_ror:1
+    return u;
 }
 
-template <int BATCH, bool FAST>
-__device__ __forceinline__ float reduce_batch(const float (&p)[BATCH], int lane)
-{
-    static_assert(BATCH == 4 || BATCH == 8, "batch of 4 or 8 samples");
-    if constexpr (BATCH == 8) return reduce8<FAST>(p, lane);
-    else return reduce4<FAST>(p, lane);
-}
-
-// lane that holds batch sample j after reduce_batch, and the sample a lane holds
+// first lane that holds partial j after reduce8 / reduce4, and the partial a lane holds after reduce4
 template <int BATCH>
 __host__ __device__ constexpr int lane_of_sample(int j)
 {
+    static_assert(BATCH == 4 || BATCH == 8, "reduce4 or reduce8");
     return BATCH == 8 ? 32 * (j & 1) + 16 * ((j >> 1) & 1) + 8 * ((j >> 2) & 1) : 32 * (j & 1) + 16 * ((j >> 1) & 1);
 }
 
-template <int BATCH>
 __device__ __forceinline__ int sample_of_lane(int lane)
 {
-    const int j = ((lane >> 5) & 1) | (((lane >> 4) & 1) << 1);
-    return BATCH == 8 ? (j | (((lane >> 3) & 1) << 2)) : j;
+    return ((lane >> 5) & 1) | (((lane >> 4) & 1) << 1);
 }
 
 __device__ __forceinline__ float wave_max(float v)
@@ -264,11 +213,9 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
-// max over the lane groups of a batch (values already uniform inside a group)
-template <int BATCH>
+// max over the four rows of reduce4 (values already uniform inside a row)
 __device__ __forceinline__ float group_max(float v)
 {
-    if constexpr (BATCH == 8) v = fmaxf(v, __shfl_xor(v, 8));
     v = fmaxf(v, __shfl_xor(v, 16));
     v = fmaxf(v, __shfl_xor(v, 32));
     return v;
@@ -383,9 +330,7 @@ int validate(const EtLayerDesc *d)
     if (d->C > 512) return fail("C=%d > 512 not supported", d->C);
     if (d->K < 2 || d->K > 256) return fail("K=%d outside [2, 256]", d->K);
     if ((long long)d->H * d->W * d->C * 4 >= (1LL << 31)) return fail("one feature map must stay below 2 GiB");
-#ifndef ET_DEV_ABLATE
-    if (d->variant & (64 | 128)) return fail("variant bits 64 / 128 (roofline ablations, wrong results) exist in -DET_DEV_ABLATE builds only");
-#endif
+    if (d->variant & (64 | 128)) return fail("variant bits 64 / 128 are reserved (they were roofline ablations with wrong results) and rejected");
     if (!(d->downsample > 0.f) || !(d->image_resize > 0.f) || !(d->predict_resize > 0.f))
         return fail("downsample / resize factors must be positive");
     return 0;

@@ -32,7 +32,6 @@ TileParams fwd_tile_params(const EtLayerDesc *desc, const TileCall &c, const flo
     p.fref = feat_ref; p.fsrc = feat_src;
     p.out = out; p.attn = attn; p.corr = corr_pos;
     p.res_bias = nullptr; p.res_base = nullptr;
-    p.interleave = 0; p.ablate = 0;
     p.blocks_per_pair = c.tiles_per_pair;
     p.total_blocks = c.total;
     tp.tiles_per_pair = c.tiles_per_pair;

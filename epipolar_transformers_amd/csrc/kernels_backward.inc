@@ -10,7 +10,7 @@
 // is evicted, i.e. once per (pixel, source row) instead of once per sample.
 // Channel mapping here is lane + 64*i (dword-strided) so that each atomic
 // instruction of a flush covers 256 contiguous bytes.
-template <int CPD /*dwords per lane: C <= 64*CPD*/, int KPL, bool FAST>
+template <int CPD /*dwords per lane: C <= 64*CPD*/, int KPL>
 __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_kernel(const BwdParams p)
 {
     // Float-atomic scatter form (no workspace needed); the default is the gather form below.
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_kernel(con
 
         const et::Segment seg = et::epipolar_segment(d, cam, p.xs[w], p.ys[h]);
         SampleTable<KPL> tb;
-        build_sample_table<KPL, true>(d, seg, p.steps, lane, row_bytes, tb);
+        build_sample_table<KPL>(d, seg, p.steps, lane, row_bytes, tb);
         float v_logit[KPL], v_da[KPL];
         bool v_masked[KPL];
 #pragma unroll
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_kernel(con
                         }
                     }
                 }
-                keep_batch<KPL, FAST>(d, K, lane, s, kb, p1, p2, v_logit, v_da, v_masked);
+                keep_batch<KPL>(d, K, lane, s, kb, p1, p2, v_logit, v_da, v_masked);
             }
         }
 
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_kernel(con
 // backward, emit form with the forward's channel mapping (float4 per lane):
 // d(feat_ref) + per-(pixel, source row) coefficients for the gather pass
 // ----------------------------------------------------------------------------
-template <int CPL, int KPL, bool FAST>
+template <int CPL, int KPL>
 __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_emit_kernel(const BwdParams p)
 {
     extern __shared__ float s_dyn[];  // per wave: [KPL*64] float4 weights, then [cap] u, [cap] alpha, [cap] beta
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_emit_kerne
         const int h = pix / W, w = pix - h * W;
         const et::Segment seg = et::epipolar_segment(d, cam, p.xs[w], p.ys[h]);
         SampleTable<KPL> tb;
-        build_sample_table<KPL, true>(d, seg, p.steps, lane, row_bytes, tb);
+        build_sample_table<KPL>(d, seg, p.steps, lane, row_bytes, tb);
         float v_logit[KPL], v_da[KPL];
         bool v_masked[KPL];
 #pragma unroll
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_emit_kerne
                         }
                     }
                 }
-                keep_batch<KPL, FAST>(d, K, lane, s, kb, p1, p2, v_logit, v_da, v_masked);
+                keep_batch<KPL>(d, K, lane, s, kb, p1, p2, v_logit, v_da, v_masked);
             }
         }
 

@@ -4,12 +4,12 @@
 // forward: fused epipolar sample + dot + masked softmax + weighted sum
 // ----------------------------------------------------------------------------
 // CPL: float4 channel groups per lane (C <= 256*CPL); KPL: samples per lane
-// (K <= 64*KPL); BATCH: samples per cross-lane reduction; FAST: permlane/DPP
-// reductions; CACHE: 2x2 tap register cache; MINW: waves per SIMD the register
-// allocator must leave room for (__launch_bounds__ second argument); RAGGED: K is
-// not a multiple of BATCH, so batches carry per-sample validity logic.
-template <int CPL, int KPL, int BATCH, bool FAST, bool CACHE, int MINW, bool RAGGED>
-__global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_kernel(const FwdParams p)
+// (K <= 64*KPL); RAGGED: the last batch of samples may be short, so batches
+// carry per-sample validity logic.  Tuned on MI355X (profiles/r01_variant_sweep_last.json):
+// cross-lane reductions per kBatch = 4 samples, and room for 5 waves per SIMD (<= 96 VGPRs).
+constexpr int kBatch = 4;
+template <int CPL, int KPL, bool RAGGED>
+__global__ __launch_bounds__(kWave *kWavesPerBlock, 5) void epipolar_fwd_kernel(const FwdParams p)
 {
     // dynamic LDS: [K][16] attention tile (only when attn is requested), then one
     // [KPL*64] float4 table of bilinear weights per wave
@@ -40,10 +40,9 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_kern
     for (int c = 0; c < CPL; ++c) voff[c] = min(lane + c * kWave, nvec - 1) * 16;
 
     for (int pp = 0; pp < kPixPerWave; ++pp) {
-        // consecutive pixels either per wave (0..3 | 4..7 | ..) or interleaved across the block's
-        // waves (wave w takes pixels w, w+4, ..), which keeps the four waves on neighbouring
-        // epipolar lines at the same time (shared rows hit in the CU's L1)
-        const int slot_in_block = p.interleave ? pp * kWavesPerBlock + wave : wave * kPixPerWave + pp;
+        // pixels interleaved across the block's waves (wave w takes pixels w, w+4, ..), which keeps the
+        // four waves on neighbouring epipolar lines at the same time (shared rows hit in the CU's L1)
+        const int slot_in_block = pp * kWavesPerBlock + wave;
         const int pix = pix_base + slot_in_block;
         if (pix >= HW) break;  // wave-uniform
         const int h = pix / W, w = pix - h * W;
@@ -51,19 +50,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_kern
         // ---- lanes <-> samples: geometry and tap table ----------------------
         const et::Segment seg = et::epipolar_segment(d, cam, p.xs[w], p.ys[h]);
         SampleTable<KPL> tb;
-        build_sample_table<KPL, CACHE>(d, seg, p.steps, lane, row_bytes, tb);
-#ifdef ET_DEV_ABLATE
-        if (p.ablate) {  // roofline ablations (results are wrong by construction; development builds only)
-#pragma unroll
-            for (int s = 0; s < KPL; ++s) {
-                if (p.ablate == 1 && (s > 0 || lane > 0)) tb.need[s] = 0;
-                if (p.ablate == 2) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) tb.off[s][r] = 0;
-                }
-            }
-        }
-#endif
+        build_sample_table<KPL>(d, seg, p.steps, lane, row_bytes, tb);
         float v_sim[KPL];
 #pragma unroll
         for (int s = 0; s < KPL; ++s) {
@@ -91,11 +78,11 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_kern
 #pragma unroll
         for (int s = 0; s < KPL; ++s) {
             const int kcount = min(kWave, K - s * kWave);  // samples held in this slot (uniform)
-            for (int kb = 0; kb < kcount; kb += BATCH) {
-                float4 S[BATCH][CPL];
-                float part[BATCH];
+            for (int kb = 0; kb < kcount; kb += kBatch) {
+                float4 S[kBatch][CPL];
+                float part[kBatch];
 #pragma unroll
-                for (int j = 0; j < BATCH; ++j) {
+                for (int j = 0; j < kBatch; ++j) {
                     const int kk = kb + j;
                     if (RAGGED) {
                         part[j] = 0.f;
@@ -127,14 +114,14 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_kern
                         }
                     }
                 }
-                // eight dot products -> 8-lane groups
-                const float u = reduce_batch<BATCH, FAST>(part, lane);
-                const bool jvalid = !RAGGED || (kb + sample_of_lane<BATCH>(lane)) < kcount;
+                // four dot products -> 16-lane rows
+                const float u = reduce4(part, lane);
+                const bool jvalid = !RAGGED || (kb + sample_of_lane(lane)) < kcount;
                 float sv = (u == 0.f) ? -1e10f : u;  // epipolar.py:298
                 float e;
                 if (d.softmax_enabled) {
                     sv = sv * d.softmax_scale;  // epipolar.py:306
-                    const float bm = group_max<BATCH>(jvalid ? sv : neg_inf);
+                    const float bm = group_max(jvalid ? sv : neg_inf);
                     const float m_new = fmaxf(m_run, bm);
                     // accumulator weights only need ~1e-6 relative accuracy (the returned attention is
                     // recomputed with expf in the final pass): hardware exp2
@@ -148,11 +135,11 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_kern
                     e = jvalid ? sv : 0.f;
                 }
                 // keep the logit of sample (kb + j) in lane (kb + j) for the final pass
-                const float mine = __shfl(sv, lane_of_sample<BATCH>(lane & (BATCH - 1)));
-                if ((lane / BATCH) == (kb / BATCH)) v_sim[s] = mine;
+                const float mine = __shfl(sv, lane_of_sample<kBatch>(lane & (kBatch - 1)));
+                if ((lane / kBatch) == (kb / kBatch)) v_sim[s] = mine;
 #pragma unroll
-                for (int j = 0; j < BATCH; ++j) {
-                    const float ej = lane_bcast(e, lane_of_sample<BATCH>(j));
+                for (int j = 0; j < kBatch; ++j) {
+                    const float ej = lane_bcast(e, lane_of_sample<kBatch>(j));
 #pragma unroll
                     for (int c = 0; c < CPL; ++c) acc[c] = f4_fma(ej, S[j][c], acc[c]);
                 }
@@ -216,8 +203,8 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_kern
 }
 
 // ----------------------------------------------------------------------------
-// forward, several pixels per wave ("multi"): PPW neighbouring pixels advance in
-// lockstep, LPP = 64 / PPW lanes each, CQ float4 channel groups per lane.
+// forward, four pixels per wave ("multi", C == 256): PPW = 4 neighbouring pixels advance
+// in lockstep, LPP = 16 lanes each, CQ = 4 float4 channel groups per lane.
 // ----------------------------------------------------------------------------
 // Why: in the one-pixel-per-wave kernel only ~13 of ~36 VALU instructions per sample
 // are arithmetic; the rest is per-sample bookkeeping (lane broadcasts, 64-lane
@@ -225,10 +212,10 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_kern
 // the per-step record (tap offsets, weights, need bits) is read from LDS by each
 // lane group, tap loads are exec-masked per group, the dot product reduces over
 // LPP lanes only, and the online soft-max runs one sample per step (no batching).
-// Requires C == 4 * LPP * CQ exactly (C = 256: PPW 2 / CQ 2 or PPW 4 / CQ 4).
-template <int PPW, int CQ, int KPL, bool PIPE, int MINW>
-__global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_multi_kernel(const FwdParams p)
+// Requires C == 4 * LPP * CQ == 256 exactly, and K <= 64 (one sample slot per lane).
+__global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_fwd_multi_kernel(const FwdParams p)
 {
+    constexpr int PPW = 4, CQ = 4, KPL = 1;
     constexpr int LPP = kWave / PPW;
     constexpr int ROUNDS = kPixPerWave / PPW;
     constexpr int KP = KPL * kWave;  // padded samples per pixel
@@ -280,7 +267,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_mult
             et::Segment seg;
             seg.sx = sq.x; seg.sy = sq.y; seg.vx = sq.z; seg.vy = sq.w;
             SampleTable<KPL> tb;
-            build_sample_table<KPL, true>(d, seg, p.steps, lane, row_bytes, tb);
+            build_sample_table<KPL>(d, seg, p.steps, lane, row_bytes, tb);
 #pragma unroll
             for (int s = 0; s < KPL; ++s) {
                 const int k = s * kWave + lane;
@@ -311,11 +298,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_mult
         // request (exec-masked per lane group) the tap rows step k does not have yet
         auto issue_step = [&](int k) {
             int4 off = s_off[rec0 + k];
-#ifdef ET_DEV_ABLATE
-            const int need = (p.ablate == 1 && k > 0) ? 0 : (off.x & 15);
-#else
             const int need = off.x & 15;
-#endif
             off.x &= ~15;
             if (need & 1) {
 #pragma unroll
@@ -334,9 +317,8 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_mult
                 for (int c = 0; c < CQ; ++c) R[3][c] = buf_load_f4(src, off.w + lane_off, c * LPP * 16);
             }
         };
-        if (PIPE) issue_step(0);
         for (int k = 0; k < K; ++k) {
-            if (!PIPE) issue_step(k);
+            issue_step(k);
             const float4 wv = s_wt[rec0 + k];
             float4 S[CQ];
             float part = 0.f;
@@ -348,12 +330,6 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_mult
                 sv = f4_fma(wv.w, R[3][c], sv);
                 S[c] = sv;
             }
-            if (PIPE) {
-                // the next step's rows fly during this step's dot product, reduction and soft-max update
-                __builtin_amdgcn_sched_barrier(0);
-                if (k + 1 < K) issue_step(k + 1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
 #pragma unroll
             for (int c = 0; c < CQ; ++c) part = (c == 0) ? f4_dot(S[c], f1[c]) : part + f4_dot(S[c], f1[c]);
             // all-reduce over the LPP lanes of the pixel
@@ -361,7 +337,6 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, MINW) void epipolar_fwd_mult
             part += dpp<0x124>(part);  // row_ror:4
             part += dpp<0x122>(part);  // row_ror:2
             part += dpp<0x121>(part);  // row_ror:1
-            if (LPP == 32) part += __shfl_xor(part, 16);
             float sv = (part == 0.f) ? -1e10f : part;  // epipolar.py:298
             float e;
             if (d.softmax_enabled) {

@@ -8,13 +8,13 @@
 // Batch kb .. kb+7 of lane slot s: sum the eight partial pairs (p1: S_k . f, p2: S_k . g) over the wave, apply the
 // `== 0 -> -1e10` mask (epipolar.py:298) and the logit scale, and hand the three values of sample kb + j to the lane
 // that owns it (lane kb + j of slot s).
-template <int KPL, bool FAST>
+template <int KPL>
 __device__ __forceinline__ void keep_batch(const EtLayerDesc &d, int K, int lane, int s, int kb, const float (&p1)[8],
                                            const float (&p2)[8], float (&v_logit)[KPL], float (&v_da)[KPL],
                                            bool (&v_masked)[KPL])
 {
-    const float u1 = reduce8<FAST>(p1, lane);
-    const float u2 = reduce8<FAST>(p2, lane);
+    const float u1 = reduce8(p1, lane);
+    const float u2 = reduce8(p2, lane);
     const bool masked = (u1 == 0.f);
     float sv = masked ? -1e10f : u1;
     sv = d.softmax_enabled ? sv * d.softmax_scale : sv / (float)K;

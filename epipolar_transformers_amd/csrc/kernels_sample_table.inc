@@ -18,7 +18,7 @@ struct SampleTable {
     float nx[KPL], ny[KPL];
 };
 
-template <int KPL, bool CACHE>
+template <int KPL>
 __device__ __forceinline__ void build_sample_table(const EtLayerDesc &d, const et::Segment &seg,
                                                    const float *__restrict__ steps, int lane, int row_bytes,
                                                    SampleTable<KPL> &t)
@@ -42,7 +42,7 @@ __device__ __forceinline__ void build_sample_table(const EtLayerDesc &d, const e
                 const int carry = __shfl(t.off[s > 0 ? s - 1 : 0][r], kWave - 1);
                 if (lane == 0) prev = carry;
             }
-            if (off >= 0 && (!CACHE || off != prev)) need |= 1 << r;
+            if (off >= 0 && off != prev) need |= 1 << r;
         }
         t.need[s] = need;
     }

@@ -55,7 +55,7 @@ typedef struct EtLayerDesc {
     int32_t src_grad_mask;     /* backward only, cfg.EPIPOLAR.OTHER_GRAD (epipolar.py:141-153):
                                   bit0 = gradient reaches feat_src through the similarity ('other1'),
                                   bit1 = through the sampled values ('other2'); reference default 3 */
-    int32_t variant;           /* kernel variant bits, 0 = library default (tuning/ablation) */
+    int32_t variant;           /* kernel variant bits, 0 = library default (testing/tuning) */
 } EtLayerDesc;
 
 /* Floats per pair in the `cam` array consumed below:
@@ -65,18 +65,12 @@ typedef struct EtLayerDesc {
  * This O(N) algebra stays on the host in float32 torch. */
 #define ET_CAM_STRIDE 27
 
-/* Variant bits (EtLayerDesc.variant).  0 selects the tuned default of the forward kernel
- * (MULTI4 for C == 256 and K <= 64, else BATCH4 | OCC5 | PIXEL_INTERLEAVE); the bits exist
- * for ablation and tuning runs. */
-#define ET_VARIANT_SAFE_REDUCE 1  /* cross-lane sums via ds_bpermute only (no permlane swaps / DPP) */
-#define ET_VARIANT_NO_TAP_CACHE 2 /* reload all four taps for every sample                          */
-#define ET_VARIANT_PIXEL_INTERLEAVE 4 /* wave w of a block takes pixels w, w+4, .. instead of 4w..4w+3 */
-#define ET_VARIANT_BATCH4 8       /* cross-lane reductions per 4 samples (fewer registers) instead of 8 */
-#define ET_VARIANT_OCC5 16        /* compile for >= 5 waves per SIMD (<= 96 VGPRs)                       */
-#define ET_VARIANT_OCC6 32        /* compile for >= 6 waves per SIMD (<= 80 VGPRs, may spill)            */
-#define ET_VARIANT_PIPELINE 512    /* multi kernels: request step k+1's rows right after step k is interpolated */
-#define ET_VARIANT_MULTI2 1024     /* C == 256: two pixels per wave in lockstep (32 lanes x 8 channels each) */
-#define ET_VARIANT_MULTI4 2048     /* C == 256: four pixels per wave in lockstep (16 lanes x 16 channels)    */
+/* Variant bits (EtLayerDesc.variant).  0 is the library default; the bits below select another kernel of a family
+ * (testing, tuning, reproducibility).  The per-pixel kernels (et_epipolar_forward / _backward) have one tuned
+ * instance per shape class -- four pixels per wave for C == 256 and K <= 64, else one pixel per wave with
+ * reductions per 4 samples -- and take it whatever else the word holds. */
+/* (bits 1, 2, 4, 8, 16, 32, 256, 512, 1024, 2048 were the per-pixel kernels' round-1 tuning switches -- reduction form, tap cache, pixel order, batch size, register budgets, pixels per wave: measured in round 1 (profiles/r01_variant_sweep_last.json), the winners are the kernels above; the bits stay accepted and now select nothing) */
+/* (bits 64 and 128 were roofline ablations that computed wrong results by construction: reserved, and rejected) */
 #define ET_VARIANT_BWD_ATOMIC 4096 /* backward: float-atomic scatter even when a workspace is given      */
 #define ET_VARIANT_BWD_UNSORTED 8192 /* backward gather: sum in arrival order (faster, not bit-reproducible) */
 #define ET_VARIANT_NO_TILE 16384  /* host wrappers: do not route C == 256 calls to et_epipolar_forward_tiled */
@@ -88,13 +82,6 @@ typedef struct EtLayerDesc {
 #define ET_VARIANT_TILE_EXACT 524288 /* et_epipolar_forward_tiled, one-block-per-tile kernel: both GEMMs in exact fp32 (v_mfma_f32_32x32x2_f32) instead of split-fp16 products */
 #define ET_VARIANT_BWD_SPLIT_IN_PLACE 2097152 /* et_epipolar_backward_tiled: split EVERY tile beyond the merged kernel's columns in place (rounds 2-4) instead of deferring the hard ones (those whose group chain would outlast the launch) to a second launch of the one-array kernel: equal to 3.5 % faster on the ring rig, 1.5-2 x slower on geometries with many such tiles */
 #define ET_VARIANT_BWD_DETERMINISTIC 4194304 /* host wrappers / the Python binding: prefer the deterministic tile backward (et_epipolar_backward_tiled_det) where the tile path applies; the kernels never look at it */
-#define ET_VARIANT_BASELINE 256    /* batches of 8, compiler-chosen registers, pixels 4w..4w+3 per wave   */
-/* Bits 64 and 128 are reserved: in development builds of the library (-DET_DEV_ABLATE) they switch the per-pixel
- * kernel's tap loads off for roofline ablations (wrong results by construction); a product build rejects them. */
-#ifdef ET_DEV_ABLATE
-#define ET_VARIANT_ABLATE_NO_LOADS 64
-#define ET_VARIANT_ABLATE_ONE_ROW 128
-#endif
 
 int et_abi_version(void);
 const char *et_last_error(void);

@@ -15,15 +15,14 @@ echo "== pytest gpu"; timeout 1500 python -m pytest tests -m gpu -q --timeout 60
 tail -25 "$OUT/pytest_gpu_$TAG.log"
 echo "== bench"; timeout 900 python bench.py --full --steps 30 --warmup 5 > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"; echo "bench exit $?"
 cat "$OUT/bench_$TAG.json"; tail -5 "$OUT/bench_$TAG.err"
-for v in 16384 256; do   # 16384: per-pixel default kernel (no MFMA tiles), 256: per-pixel baseline variant
-  timeout 600 python bench.py --full --steps 10 --warmup 3 --variant $v --no-cpu-baseline > "$OUT/bench_${TAG}_variant$v.json" 2>> "$OUT/bench_$TAG.err"
-  python - <<PY
+v=16384   # the per-pixel kernels (no MFMA tiles)
+timeout 600 python bench.py --full --steps 10 --warmup 3 --variant $v --no-cpu-baseline > "$OUT/bench_${TAG}_variant$v.json" 2>> "$OUT/bench_$TAG.err"
+python - <<PY
 import json
 try:
     r=json.load(open("$OUT/bench_${TAG}_variant$v.json")); print("variant $v kernel_ms", r["roofline"]["kernel_ms"], "step ms", r["ms_per_step"])
 except Exception as e: print("variant $v failed", e)
 PY
-done
 echo "== rocprof"
 cd /tmp && export TMPDIR=/tmp
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$TAG" -o trace -- python "$ROOT/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline > "$OUT/rocprof_$TAG.log" 2>&1; echo "rocprof exit $?"
