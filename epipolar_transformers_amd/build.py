@@ -30,6 +30,7 @@ UNITS = {
     "et_misc.hip": ["kernels_misc.inc"],
     "et_residual_gemm.hip": ["kernels_residual_gemm.inc", "et_wave_reduce.h"],
     "et_triangulate.hip": ["et_triangulate.h", "et_wave_reduce.h"],
+    "et_rpsm.hip": ["et_rpsm.h"],
 }
 LIB = os.path.join(PKG, "lib", "libepipolar_amd.so")
 OBJ = os.path.join(PKG, "lib", "obj")

@@ -143,6 +143,13 @@ def default_cfg() -> CfgNode:
     C.KEYPOINT.NUM_PTS = 21
     C.KEYPOINT.HEATMAP_SIZE = (224, 224)
     C.KEYPOINT.NFEATS = 256
+    C.KEYPOINT.ROOTIDX = 0
+    C.PICT_STRUCT = LenientCfgNode()          # KEYPOINT.TRIANGULATION rpsm (core/config.py:123-129; PAIRWISE_FILE is not read:
+    C.PICT_STRUCT.FIRST_NBINS = 16            #  limb compatibility is the distance band of ops.rpsm)
+    C.PICT_STRUCT.RECUR_NBINS = 2
+    C.PICT_STRUCT.RECUR_DEPTH = 10
+    C.PICT_STRUCT.LIMB_LENGTH_TOLERANCE = 150
+    C.PICT_STRUCT.GRID_SIZE = 2000
     C.EPIPOLAR = LenientCfgNode()
     C.EPIPOLAR.VIS = False
     C.EPIPOLAR.TOPK = 1

@@ -24,6 +24,8 @@
 //                                                    batch statistics / backward (et_residual_gemm, et_z_*)
 //   et_triangulate.hip    et_triangulate.h           KEYPOINT.TRIANGULATION epipolar / epipolar_dlt: one wave per (frame, joint), a
 //                                                    lane per hypothesis, float64 Givens + Jacobi SVD; host + device routine
+//   et_rpsm.hip           et_rpsm.h                  KEYPOINT.TRIANGULATION rpsm: unary / max-product message / per-frame recursion
+//                                                    kernels, float32, no pairwise table; host + device routine
 //   et_misc.hip           kernels_misc.inc           sample_locs, residual epilogue, NCHW <-> NHWC, ABI version / errors
 //   et_wave_reduce.h                                 DPP wave reductions (wave_all_sum / max / min): general, tile, GEMM units
 //   et_split_f16.h                                   fp32 -> two fp16 halves for the matrix cores (tile units)

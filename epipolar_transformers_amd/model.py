@@ -12,7 +12,9 @@ What changes against the reference:
   * N3 -- test-time lifting stays on the GPU: batched float64 SVD-DLT (`triangulate.py`) instead of the per-joint
     pymvg loop on the CPU (vision/triangulation.py:400-441), no device-to-host copy of the detections; with
     KEYPOINT.TRIANGULATION epipolar / epipolar_dlt the reference's `triangulate_epipolar` (:234-348), which consumes the
-    layer's corr_pos, as one HIP kernel (`ops.triangulate_epipolar`).
+    layer's corr_pos, as one HIP kernel (`ops.triangulate_epipolar`); with KEYPOINT.TRIANGULATION rpsm and the batch's `rpsm`
+    dict the recursive pictorial structure model (modeling/pictorial_cuda.py:222-254) on the heat maps, all frames at once
+    (`ops.rpsm`).
   * `EPIPOLAR.MULTITEST` (model.py:213-239): every other view in turn as the source, per joint the detection with
     the highest score -- here all (reference, source) combinations go through ONE launch of the fused layer.
   * `BACKBONE.SYNC_BN` converts through `parallel.convert_sync_batchnorm` (model.py:56-58).
@@ -157,14 +159,19 @@ class MultiViewPoseModel(nn.Module):
 
     # ------------------------------------------------------------------------------------------ N3
     def lift(self, batch_locs: torch.Tensor, batch_scos: torch.Tensor, KRT: torch.Tensor, num_views: int,
-             corr_pos: torch.Tensor = None, other_KRT: torch.Tensor = None):
+             corr_pos: torch.Tensor = None, other_KRT: torch.Tensor = None, *, rpsm: dict = None,
+             heatmaps: torch.Tensor = None):
         """(F*V, J, 2) detections -> (F, J, 3) world points, on the device the detections live on, by the method
         cfg.KEYPOINT.TRIANGULATION names (model.py:295-311):
           epipolar / epipolar_dlt   triangulate_epipolar (vision/triangulation.py:234-348) as one HIP kernel
                                     (ops.triangulate_epipolar); needs the layer's corr_pos (F*V,H,W,2) and the projections of
                                     the source views other_KRT (F*V,3,4), with KEYPOINT.CONF_THRES / RANSAC_THRES;
+          rpsm                      with the batch's `rpsm` dict (forward's docstring): the recursive pictorial structure model
+                                    (modeling/pictorial_cuda.py:222-254) as HIP kernels (ops.rpsm) on the heat maps
+                                    (F*V,J,H,W), with PICT_STRUCT.* and limb compatibility as a distance band instead of
+                                    PICT_STRUCT.PAIRWISE_FILE; without the dict it takes the next row;
           anything else             the thresholded linear DLT of triangulate.py (the reference's `pymvg`; its always-random
-                                    `naive` / `refine` and `rpsm` are not restated and take this path too)."""
+                                    `naive` / `refine` are not restated and take this path too)."""
         cfg = self.cfg
         m, j, _ = batch_locs.shape
         f = m // num_views
@@ -183,6 +190,26 @@ class MultiViewPoseModel(nn.Module):
                 corr_pos.reshape(f, num_views, *corr_pos.shape[-3:]).contiguous(), downsample=float(cfg.BACKBONE.DOWNSAMPLE),
                 resize=scale, conf_thres=float(getattr(cfg.KEYPOINT, "CONF_THRES", 0.05)),
                 ransac_thres=float(getattr(cfg.KEYPOINT, "RANSAC_THRES", 3)), dlt=method == "epipolar_dlt")
+        if method == "rpsm" and rpsm is not None:
+            if heatmaps is None:
+                raise ValueError("KEYPOINT.TRIANGULATION rpsm scores the heat maps, and EPIPOLAR.MULTITEST keeps none (every other "
+                                 "view is the source in turn): use pymvg with it")
+            from . import pictorial
+            from .config import amd_knob
+
+            dev, ps = heatmaps.device, cfg.PICT_STRUCT
+            image_size = tuple(cfg.DATASETS.IMAGE_SIZE)
+            f32 = lambda t, *shape: torch.as_tensor(t).to(dev, torch.float32).reshape(*shape).contiguous()
+            limbs = lambda t: None if t is None else f32(t, *((-1, j - 1) if torch.as_tensor(t).dim() > 1 else (j - 1,)))
+            return ops.rpsm(
+                heatmaps.detach().to(torch.float32).reshape(f, num_views, *heatmaps.shape[-3:]).contiguous(),
+                f32(rpsm["cameras"], f, num_views, 3, 4),
+                pictorial.crop_transform(f32(rpsm["crop_center"], f, num_views, 2), f32(rpsm["crop_scale"], f, num_views, -1),
+                                         image_size).contiguous(),
+                f32(rpsm["center"], f, 3), limbs(rpsm["limb_length"]), first_limb_length=limbs(rpsm.get("first_limb_length")),
+                parent=rpsm.get("parent"), image_size=image_size, grid_size=float(ps.GRID_SIZE), first_nbins=int(ps.FIRST_NBINS),
+                recur_nbins=int(ps.RECUR_NBINS), recur_depth=int(ps.RECUR_DEPTH), tolerance=float(ps.LIMB_LENGTH_TOLERANCE),
+                align_corners=bool(amd_knob(cfg, "ALIGN_CORNERS", False)))
         return triangulate_dlt(pts, KRT.to(batch_locs.device).view(f, num_views, 3, 4), batch_scos.view(f, num_views, j),
                                conf_thres=float(getattr(cfg.KEYPOINT, "CONF_THRES", 0.05)))
 
@@ -191,7 +218,10 @@ class MultiViewPoseModel(nn.Module):
         """The multiview_keypoint branch of Modelbuilder.forward (model.py:160-302).  `inputs` holds the reference's
         keys: img, KRT, and either `other_index` (rows of the source views inside `img`: the de-duplicated path) or
         `other_img` + `other_KRT` (the reference's two-pass form); optional heatmap / visibility (loss) and points-3d
-        (MPJPE).  Returns (loss_dict, metric_dict) in training, (loss_dict, metric_dict, out) otherwise, as the reference does
+        (MPJPE); optional `rpsm`, what KEYPOINT.TRIANGULATION rpsm needs (model.py:312-334): a dict of `cameras` (F*V,3,4: origK @ RT),
+        `crop_center` (F*V,2), `crop_scale` (F*V,2) or (F*V,), `center` (F,3), `limb_length` (F,J-1) or (J-1,) and optionally
+        `first_limb_length`, `parent` -- the reference takes centre and limb lengths from the first frame's ground truth, here
+        the caller supplies them per frame.  Returns (loss_dict, metric_dict) in training, (loss_dict, metric_dict, out) otherwise, as the reference does
         (model.py:478-493)."""
         cfg = self.cfg
         img = inputs["img"]
@@ -225,7 +255,8 @@ class MultiViewPoseModel(nn.Module):
                    batch_locs=batch_locs, score_pred=batch_scos, batch_scos=batch_scos,
                    heatmaps=heat[0] if heat is not None else None)
         if not is_train and cfg.VIS.MULTIVIEW:
-            pred = self.lift(batch_locs, batch_scos, KRT, views, corr_pos, other_KRT)
+            pred = self.lift(batch_locs, batch_scos, KRT, views, corr_pos, other_KRT, rpsm=inputs.get("rpsm"),
+                             heatmaps=heat[0] if heat is not None else None)
             out["points-3d"] = pred
             if inputs.get("points-3d") is not None:
                 gt = inputs["points-3d"].to(pred.device).view(-1, views, pred.shape[1], 3)[:, 0]

@@ -849,6 +849,68 @@ def triangulate_epipolar(pts: torch.Tensor, conf: torch.Tensor, krt: torch.Tenso
     return (out, info) if want_info else out
 
 
+def rpsm_workspace_bytes(frames: int, joints: int, first_nbins: int, recur_nbins: int) -> int:
+    return int(_lib.load().et_rpsm_workspace_bytes(int(frames), int(joints), int(first_nbins), int(recur_nbins)))
+
+
+def rpsm(heatmaps: torch.Tensor, cams: torch.Tensor, trans: torch.Tensor, center: torch.Tensor, limb_length: torch.Tensor, *,
+         first_limb_length: torch.Tensor = None, parent=None, image_size, grid_size: float, first_nbins: int, recur_nbins: int,
+         recur_depth: int, tolerance: float, align_corners: bool = False, want_path: bool = False, workspace: torch.Tensor = None):
+    """KEYPOINT.TRIANGULATION rpsm: the recursive pictorial structure model of modeling/pictorial_cuda.py:222-254 for all frames
+    in three kinds of HIP kernel (et_rpsm: unary, one max-product launch per tree level, one block per frame for the back-track and
+    the RECUR_DEPTH levels), float32 as the reference.  heatmaps (F,V,J,H,W); cams (F,V,3,4): projections to image pixels (the
+    reference's origK @ RT); trans (F,V,2,3): the crop transforms (pictorial.crop_transform); center (F,3): the first grid's centre;
+    limb_length (F,E) or (E,), E = J - 1: limb e ends at the e-th non-root joint in ascending order; first_limb_length: the first
+    stage's lengths (None: limb_length); parent: J entries, the root has -1 (None: the H36M skeleton, pictorial.H36M_PARENT);
+    image_size (w, h) = DATASETS.IMAGE_SIZE.  Returns the (F,J,3) float32 pose -- and, with `want_path`, the (F,1+recur_depth,J)
+    int32 bins chosen at every level.  `workspace`: a uint8 buffer of at least rpsm_workspace_bytes(...) bytes, any alignment (None:
+    allocated here).
+
+    One deviation from the reference: limb compatibility is the band | ||x_a - x_c + 1e-6|| + 1e-9 - L | < tolerance computed from
+    the bin positions, which is what the reference's own compute_pairwise builds for the recursion levels; its first stage reads a
+    precomputed 0/1 table (PICT_STRUCT.PAIRWISE_FILE) instead, and a table that is not such a band cannot be expressed.
+    No gradient."""
+    _require_gpu(heatmaps, "heatmaps")
+    if heatmaps.dim() != 5:
+        raise ValueError("heatmaps must be (F,V,J,H,W), got %s" % (tuple(heatmaps.shape),))
+    f, v, j, h, w = heatmaps.shape
+    dev = heatmaps.device
+    _require_f32(heatmaps, "heatmaps", dev)
+    _require_f32(cams, "cams", dev, (f, v, 3, 4))
+    _require_f32(trans, "trans", dev, (f, v, 2, 3))
+    _require_f32(center, "center", dev, (f, 3))
+
+    def limbs(t, name):
+        _require_gpu(t, name)
+        if tuple(t.shape) == (j - 1,):
+            t = t.expand(f, j - 1).contiguous()
+        _require_f32(t, name, dev, (f, j - 1), "%s must be a contiguous float32 tensor of shape %s or %s on %s, got %s on %s" % (
+            name, (f, j - 1), (j - 1,), dev, tuple(t.shape), t.device))
+        return t
+
+    limb_length = limbs(limb_length, "limb_length")
+    if first_limb_length is not None:
+        first_limb_length = limbs(first_limb_length, "first_limb_length")
+    if parent is None:
+        from .pictorial import H36M_PARENT as parent
+    parent = [int(p) for p in parent]
+    if len(parent) != j:
+        raise ValueError("parent names %d joints, heatmaps have %d" % (len(parent), j))
+    parent_c = (ctypes.c_int32 * j)(*parent)
+    need = rpsm_workspace_bytes(f, j, first_nbins, recur_nbins)
+    if workspace is None:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    else:
+        _require_bytes(workspace, "workspace", need, dev)
+    out = _empty((f, j, 3), device=dev)
+    path = torch.empty((f, 1 + max(int(recur_depth), 0), j), dtype=torch.int32, device=dev) if want_path else None
+    _call("et_rpsm", heatmaps, f, v, j, h, w, _ptr(heatmaps), _ptr(cams), _ptr(trans), _ptr(center), _ptr(limb_length),
+          _ptr(first_limb_length), parent_c, float(image_size[0]), float(image_size[1]), float(grid_size), int(first_nbins),
+          int(recur_nbins), int(recur_depth), float(tolerance), int(bool(align_corners)), _ptr(out), _ptr(path), _ptr(workspace),
+          workspace.numel(), _stream(heatmaps))
+    return (out, path) if want_path else out
+
+
 class EpipolarAttend(torch.autograd.Function):
     """out = sum_k softmax_k(scale * mask(f_ref . S_k)) S_k with S_k the K bilinear
     samples of f_src on the pixel's epipolar segment (epipolar.py:188-247).

@@ -445,6 +445,39 @@ int et_debug_host_triangulate_epipolar(int32_t F, int32_t V, int32_t J, int32_t 
                                        float resize, double conf_thres, double ransac_thres, int32_t dlt, double *out,
                                        int32_t *info);
 
+/* KEYPOINT.TRIANGULATION rpsm: the recursive pictorial structure model (modeling/pictorial_cuda.py:222-254) for F frames at once,
+ * float32 as the reference.  A first stage scores first_nbins^3 candidate positions per joint (a grid of grid_size around
+ * center[f]) against every view's heat map and runs max-product over the limbs of the skeleton; recur_depth levels follow, each
+ * with a grid of recur_nbins^3 bins around every joint's current position, of size grid_size / first_nbins / recur_nbins^k.
+ *   heatmaps : (F, V, J, H, W) ;  cams : (F, V, 3, 4) projections to IMAGE pixels ;  trans : (F, V, 2, 3) crop transforms
+ *   center   : (F, 3) ;  limb_length : (F, J - 1), limb e ends at the e-th non-root joint in ascending order
+ *   first_limb_length : as limb_length, for the first stage; NULL = limb_length
+ *   parent   : J int32 on the HOST, the root has -1 ;  image_w / image_h : cfg.DATASETS.IMAGE_SIZE
+ *   out      : (F, J, 3) ;  path : (F, 1 + recur_depth, J) int32 or NULL, the chosen bin of every level
+ * A bin: b = (ix * n + iy) * n + iz at linspace(-size/2, size/2, n)[i] + centre per axis.  Its unary: the sum over the views, in
+ * ascending order, of one bilinear sample (zero padding; align_corners as given) of heatmaps[f, v, j] at the projection
+ * p = cam . (X, 1), xy = p[:2] / p[2], through trans, times (W, H) / (image_w, image_h), normalised as xy / (H - 1, W - 1) * 2 - 1
+ * (x by H - 1: the reference's).  Parent bin a and child bin c of a limb of length L are compatible when
+ * | ||x_a - x_c + 1e-6|| + 1e-9 - L | < tolerance: this band stands in for the reference's PICT_STRUCT.PAIRWISE_FILE, and a file that
+ * is not such a band cannot be expressed.  E_j = unary_j times, for each child in ascending joint index, max_c(compat(a, c) *
+ * E_child[c]); every arg-max is the FIRST index among equal values; the root takes the arg-max of its energy and the children
+ * follow the remembered indices.
+ * Limits: V in [1, 8], J in [1, 32] with parent a tree that has one root, first_nbins in [2, 16], recur_nbins in [2, 3],
+ * recur_depth in [0, 16].  The workspace (et_rpsm_workspace_bytes; 0 for sizes outside the limits) may have any alignment and
+ * needs no initialisation.  No atomics: bit-reproducible. */
+size_t et_rpsm_workspace_bytes(int32_t F, int32_t J, int32_t first_nbins, int32_t recur_nbins);
+int et_rpsm(int32_t F, int32_t V, int32_t J, int32_t H, int32_t W, const float *heatmaps, const float *cams, const float *trans,
+            const float *center, const float *limb_length, const float *first_limb_length, const int32_t *parent, float image_w,
+            float image_h, double grid_size, int32_t first_nbins, int32_t recur_nbins, int32_t recur_depth, float tolerance,
+            int32_t align_corners, float *out, int32_t *path, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Test hook (HOST pointers, runs on the CPU, no GPU needed): the per-frame routine of et_rpsm (csrc/et_rpsm.h, its pieces shared
+ * with the kernels) in a serial loop over frames, joints and bins.  Not a CPU fallback of the path. */
+int et_debug_host_rpsm(int32_t F, int32_t V, int32_t J, int32_t H, int32_t W, const float *heatmaps, const float *cams,
+                       const float *trans, const float *center, const float *limb_length, const float *first_limb_length,
+                       const int32_t *parent, float image_w, float image_h, double grid_size, int32_t first_nbins,
+                       int32_t recur_nbins, int32_t recur_depth, float tolerance, int32_t align_corners, float *out, int32_t *path);
+
 /* Layout converters between the reference's NCHW and the kernels' NHWC. */
 int et_nchw_to_nhwc(int32_t N, int32_t C, int32_t H, int32_t W, const float *src, float *dst, void *stream);
 int et_nhwc_to_nchw(int32_t N, int32_t C, int32_t H, int32_t W, const float *src, float *dst, void *stream);
