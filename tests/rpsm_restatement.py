@@ -237,19 +237,29 @@ def ring_rig(V, rng):
 
 
 def frame(seed, V, J, H, W, *, image_size=(256, 256), box=500.0, shift_view=None, zero_joint=None, first_scale=None,
-          align_corners=False, sigma=1.5, noise=0.02):
-    """One frame's float32 inputs: a random pose on the first J joints of the H36M tree (limbs of 200-400 mm), Gaussians of
+          align_corners=False, sigma=1.5, noise=0.02, parent=None):
+    """One frame's float32 inputs: a random pose on `parent` (J entries, the root has -1; None: the first J joints of the H36M
+    tree) with limbs of 200-400 mm -- limb e ends at the e-th non-root joint in ascending order --, Gaussians of
     `sigma` map pixels where the unary term will look for each joint plus `noise` * uniform clutter, rounded to float16 values
     (that is how the fixture stores them).  shift_view: that view's crop box is moved by 60 % of its width, so part of every grid
     samples outside the map; zero_joint: that joint's maps are zero in every view."""
     rng = np.random.default_rng(seed)
-    parent = H36M_PARENT[:J]
+    parent = H36M_PARENT[:J] if parent is None else tuple(int(p) for p in parent)
+    assert len(parent) == J
+    root = parent.index(-1)
     K, RT = ring_rig(V, rng)
     X = np.zeros((J, 3))
-    X[0] = np.array([0, 0, 900.0]) + rng.normal(0, 100, 3)
-    for j in range(1, J):
-        d = rng.normal(0, 1, 3)
-        X[j] = X[parent[j]] + d / np.linalg.norm(d) * rng.uniform(200, 400)
+    X[root] = np.array([0, 0, 900.0]) + rng.normal(0, 100, 3)
+    placed, pending = {root}, [j for j in range(J) if j != root]
+    while pending:                                               # ascending passes, a joint once its parent stands (H36M: one pass)
+        before = len(pending)
+        for j in list(pending):
+            if parent[j] in placed:
+                d = rng.normal(0, 1, 3)
+                X[j] = X[parent[j]] + d / np.linalg.norm(d) * rng.uniform(200, 400)
+                placed.add(j)
+                pending.remove(j)
+        assert len(pending) < before, "parent is not a tree with one root"
     cams = (K @ RT).astype(np.float32)
     trans = np.zeros((V, 2, 3), np.float32)
     centers = np.zeros((V, 2), np.float32)
@@ -268,8 +278,8 @@ def frame(seed, V, J, H, W, *, image_size=(256, 256), box=500.0, shift_view=None
     if zero_joint is not None:
         heat[:, zero_joint] = 0
     heat = heat.astype(np.float16).astype(np.float32)
-    limb = np.array([np.linalg.norm(X[j] - X[parent[j]]) for j in range(1, J)], np.float32)
-    out = dict(heat=heat, cams=cams, trans=trans, center=(X[0] + rng.normal(0, 30, 3)).astype(np.float32), limb_length=limb, X_true=X,
+    limb = np.array([np.linalg.norm(X[j] - X[parent[j]]) for j in range(J) if j != root], np.float32)
+    out = dict(heat=heat, cams=cams, trans=trans, center=(X[root] + rng.normal(0, 30, 3)).astype(np.float32), limb_length=limb, X_true=X,
                box_center=centers, box_scale=np.float32(box / 200.0))
     if first_scale is not None:
         out["first_limb_length"] = (limb * first_scale).astype(np.float32)
@@ -279,29 +289,31 @@ def frame(seed, V, J, H, W, *, image_size=(256, 256), box=500.0, shift_view=None
 ARRAYS = ("heat", "cams", "trans", "center", "limb_length")
 
 
-def run(fr, params):
-    """The restatement on one frame dict (or a stacked scene) with `params` (the keyword arguments of rpsm)."""
+def run(fr, params, parent=None):
+    """The restatement on one frame dict (or a stacked scene) with `params` (the keyword arguments of rpsm) on the tree `parent`
+    (None: the H36M prefix of the scene's joint count)."""
     one = fr["heat"].ndim == 4
     args = [fr[k][None] if one else fr[k] for k in ARRAYS]
     first = fr.get("first_limb_length")
     return rpsm(*args, first_limb_length=None if first is None else (first[None] if one else first),
-                parent=H36M_PARENT[:fr["heat"].shape[-3]], **params)
+                parent=H36M_PARENT[:fr["heat"].shape[-3]] if parent is None else parent, **params)
 
 
 def condition_holds(margins, band):
     return bool((margins >= MARGIN).all() and (band >= BAND_MARGIN).all())
 
 
-def scene(seed, F, V, J, H, W, params, log=None, **kw):
+def scene(seed, F, V, J, H, W, params, log=None, parent=None, **kw):
     """F frames whose every decision on the chosen path is clear (margins >= 1e-4, band_margin >= 1e-2 mm): frame i starts from
     seed + 1000 * i, and a seed that violates the condition is replaced by the next one (reported through `log`).  Returns the
-    stacked float32 arrays and the restatement's (pose, path, margins, band_margin)."""
+    stacked float32 arrays and the restatement's (pose, path, margins, band_margin).  `parent`: the tree (None: the H36M prefix)."""
     frames, results = [], []
     for i in range(F):
         s = seed + 1000 * i
         while True:
-            fr = frame(s, V, J, H, W, image_size=params["image_size"], align_corners=params.get("align_corners", False), **kw)
-            res = run(fr, params)
+            fr = frame(s, V, J, H, W, image_size=params["image_size"], align_corners=params.get("align_corners", False),
+                       parent=parent, **kw)
+            res = run(fr, params, parent)
             if condition_holds(res[2], res[3]):
                 break
             if log is not None:
