@@ -23,7 +23,8 @@
 //   et_residual_gemm.hip  kernels_residual_gemm.inc  x = feat + bias + out . Wf^T as a split-fp16 GEMM, and the z branch's
 //                                                    batch statistics / backward (et_residual_gemm, et_z_*)
 //   et_triangulate.hip    et_triangulate.h           KEYPOINT.TRIANGULATION epipolar / epipolar_dlt: one wave per (frame, joint), a
-//                                                    lane per hypothesis, float64 Givens + Jacobi SVD; host + device routine
+//                                                    lane per hypothesis, float64 Givens + Jacobi SVD; host + device routine.
+//                                                    pymvg / naive / refine (et_triangulate_views): a lane per joint / the same
 //   et_rpsm.hip           et_rpsm.h                  KEYPOINT.TRIANGULATION rpsm: unary / max-product message / per-frame recursion
 //                                                    kernels, float32, no pairwise table; host + device routine
 //   et_misc.hip           kernels_misc.inc           sample_locs, residual epilogue, NCHW <-> NHWC, ABI version / errors

@@ -8,6 +8,8 @@
 //                          passes within ransac_thres of it
 //   finish_hypothesis()    what the best hypothesis returns: nothing (no inlier), its own point, or the DLT over its inliers
 //
+// The second half of the file is KEYPOINT.TRIANGULATION pymvg / naive / refine (et_triangulate_views), built from the same pieces.
+//
 // The kernel gives every lane one hypothesis and picks the winner with a wave arg-max; the host hook walks them in a loop.  Both
 // take the FIRST hypothesis with the largest count, so they agree.
 //
@@ -329,6 +331,118 @@ inline void joint_serial(const Problem &pr, int f, int j)
     double X[3];
     const int bits = finish_hypothesis(pr, f, j, best, X);
     store(pr, f, j, X, s.mask | bits);
+}
+
+// ---- KEYPOINT.TRIANGULATION pymvg / naive / refine (vision/triangulation.py:425-441, 99-154, 162-232) ----------------------------
+// The methods that need only detections, scores and projections.  They share solve_views / evaluate_hypothesis with the epipolar
+// method above (a Problem without corr_pos) and add the two selection rules and a finish of their own.  The info word has its
+// own layout:
+//   bits 0-7  : views selected                bits 8-15 : the views the returned point was computed from (none: 0)
+//   bit 18    : zeros written (no hypothesis had an inlier, or fewer than two views were selected)
+//   bits 24-30: threshold steps taken (pymvg)
+constexpr int kMethodPymvg = 0, kMethodNaive = 1, kMethodRefine = 2;
+constexpr int kInfoZeros = kInfoNoInlier;
+constexpr int kInfoStepsShift = 24;
+constexpr double kMaxConfThres = 2.0;    // bounds the lowering loop of pymvg: (2 + 1) / 0.05 + 1 = 61 steps
+
+struct ViewsProblem {
+    Problem pr;          // H, W, other_krt, corr_pos, ds, resize, dlt unused
+    double conf_thres;   // pymvg lowers it in float64 and compares in float32
+    int method;
+};
+
+ET_TRI_HD void store_zeros(const Problem &pr, int f, int j, int info)
+{
+    const double Z[3] = {0.0, 0.0, 0.0};
+    store(pr, f, j, Z, info | kInfoZeros);
+}
+
+// pymvg: the views with conf > float32(t), t lowered by 0.05 (repeated float64 subtraction: the rounding of the sequence is part
+// of the rule) while at most one view is selected and t >= -1; then the DLT over them.  The reference fails or returns a
+// rank-deficient vector when the loop ends with fewer than two views (V = 1, NaN scores, scores <= -1): zeros and the flag here.
+ET_TRI_HD void pymvg_joint(const ViewsProblem &vp, int f, int j)
+{
+    const Problem &pr = vp.pr;
+    float c[kMaxViews];
+#pragma unroll
+    for (int v = 0; v < kMaxViews; ++v) c[v] = v < pr.V ? pr.conf[view_row(pr, f, v) * pr.J + j] : -INFINITY;
+    double t = vp.conf_thres;
+    int mask, n, steps = 0;
+    for (;;) {
+        const float tf = (float)t;
+        mask = 0;
+        n = 0;
+#pragma unroll
+        for (int v = 0; v < kMaxViews; ++v)
+            if (c[v] > tf) {
+                mask |= 1 << v;
+                ++n;
+            }
+        if (t < -1.0 || n > 1) break;
+        t -= 0.05;
+        ++steps;
+    }
+    const int word = mask | steps << kInfoStepsShift;
+    if (n < 2) {
+        store_zeros(pr, f, j, word);
+        return;
+    }
+    double X[3];
+    solve_views(pr, f, j, mask, X);
+    store(pr, f, j, X, word | mask << 8);
+}
+
+// naive / refine: the views above float32(conf_thres), no lowering
+ET_TRI_HD int select_above(const Problem &pr, int f, int j, int &n)
+{
+    int mask = 0;
+    n = 0;
+    for (int v = 0; v < pr.V; ++v)
+        if (pr.conf[view_row(pr, f, v) * pr.J + j] > pr.conf_thres) {
+            mask |= 1 << v;
+            ++n;
+        }
+    return mask;
+}
+
+// What the best hypothesis returns.  naive: its own point.  refine: the DLT over its inliers when it has MORE THAN ONE
+// (triangulation.py:226; the epipolar method's finish_hypothesis asks for more than two).
+ET_TRI_HD void finish_views(const ViewsProblem &vp, int f, int j, int selected, const Hypothesis &best)
+{
+    const Problem &pr = vp.pr;
+    if (best.count <= 0) {
+        store_zeros(pr, f, j, selected);
+        return;
+    }
+    if (vp.method == kMethodRefine && best.count > 1) {
+        double X[3];
+        solve_views(pr, f, j, best.inliers, X);
+        store(pr, f, j, X, selected | best.inliers << 8);
+        return;
+    }
+    store(pr, f, j, best.p, selected | best.pair << 8);
+}
+
+// the whole joint of any of the three methods, hypotheses one after the other (the host hook)
+inline void views_joint_serial(const ViewsProblem &vp, int f, int j)
+{
+    const Problem &pr = vp.pr;
+    if (vp.method == kMethodPymvg) {
+        pymvg_joint(vp, f, j);
+        return;
+    }
+    int n;
+    const int selected = select_above(pr, f, j, n);
+    if (n < 2) {
+        store_zeros(pr, f, j, selected);
+        return;
+    }
+    Hypothesis best{-1, 0, 0, {0.0, 0.0, 0.0}};
+    for (int h = 0; h < pr.V * (pr.V - 1) / 2; ++h) {
+        const Hypothesis hy = evaluate_hypothesis(pr, f, j, selected, h);
+        if (hy.count > best.count) best = hy;
+    }
+    finish_views(vp, f, j, selected, best);
 }
 
 #undef ET_TRI_HD

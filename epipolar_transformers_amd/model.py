@@ -14,7 +14,8 @@ What changes against the reference:
     KEYPOINT.TRIANGULATION epipolar / epipolar_dlt the reference's `triangulate_epipolar` (:234-348), which consumes the
     layer's corr_pos, as one HIP kernel (`ops.triangulate_epipolar`); with KEYPOINT.TRIANGULATION rpsm and the batch's `rpsm`
     dict the recursive pictorial structure model (modeling/pictorial_cuda.py:222-254) on the heat maps, all frames at once
-    (`ops.rpsm`).
+    (`ops.rpsm`); with EPIPOLAR_AMD.LIFT_KERNELS, pymvg / naive / refine (:425-441, 99-154, 162-232) as one HIP launch
+    (`ops.triangulate_views`) instead of the torch DLT.
   * `EPIPOLAR.MULTITEST` (model.py:213-239): every other view in turn as the source, per joint the detection with
     the highest score -- here all (reference, source) combinations go through ONE launch of the fused layer.
   * `BACKBONE.SYNC_BN` converts through `parallel.convert_sync_batchnorm` (model.py:56-58).
@@ -170,8 +171,12 @@ class MultiViewPoseModel(nn.Module):
                                     (modeling/pictorial_cuda.py:222-254) as HIP kernels (ops.rpsm) on the heat maps
                                     (F*V,J,H,W), with PICT_STRUCT.* and limb compatibility as a distance band instead of
                                     PICT_STRUCT.PAIRWISE_FILE; without the dict it takes the next row;
-          anything else             the thresholded linear DLT of triangulate.py (the reference's `pymvg`; its always-random
-                                    `naive` / `refine` are not restated and take this path too)."""
+          anything else             the thresholded linear DLT of triangulate.py (the reference's `pymvg`); `naive` / `refine`
+                                    take this path too -- unless EPIPOLAR_AMD.LIFT_KERNELS is set.  Then pymvg / naive /
+                                    refine (:425-441, 99-154, 162-232) run as HIP kernels (ops.triangulate_views, which states
+                                    how the random pairs of naive / refine are enumerated) from the detections, scores and
+                                    projections alone, so all three also work with EPIPOLAR.MULTITEST; rpsm without its dict
+                                    is pymvg, and an unknown name is a ValueError."""
         cfg = self.cfg
         m, j, _ = batch_locs.shape
         f = m // num_views
@@ -210,6 +215,20 @@ class MultiViewPoseModel(nn.Module):
                 parent=rpsm.get("parent"), image_size=image_size, grid_size=float(ps.GRID_SIZE), first_nbins=int(ps.FIRST_NBINS),
                 recur_nbins=int(ps.RECUR_NBINS), recur_depth=int(ps.RECUR_DEPTH), tolerance=float(ps.LIMB_LENGTH_TOLERANCE),
                 align_corners=bool(amd_knob(cfg, "ALIGN_CORNERS", False)))
+        from .config import amd_knob
+
+        if amd_knob(cfg, "LIFT_KERNELS", False):
+            if method == "rpsm":
+                method = "pymvg"
+            if method not in ops.VIEW_METHODS:
+                raise ValueError("KEYPOINT.TRIANGULATION %r is none of %s" % (
+                    method, ", ".join(["epipolar", "epipolar_dlt", "rpsm"] + list(ops.VIEW_METHODS))))
+            dev = batch_locs.device
+            return ops.triangulate_views(
+                pts.contiguous(), batch_scos.reshape(f, num_views, j).contiguous(),
+                KRT.to(dev, torch.float32).reshape(f, num_views, 3, 4).contiguous(), method=method,
+                conf_thres=float(getattr(cfg.KEYPOINT, "CONF_THRES", 0.05)),
+                ransac_thres=float(getattr(cfg.KEYPOINT, "RANSAC_THRES", 3)))
         return triangulate_dlt(pts, KRT.to(batch_locs.device).view(f, num_views, 3, 4), batch_scos.view(f, num_views, j),
                                conf_thres=float(getattr(cfg.KEYPOINT, "CONF_THRES", 0.05)))
 

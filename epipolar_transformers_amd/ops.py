@@ -849,6 +849,41 @@ def triangulate_epipolar(pts: torch.Tensor, conf: torch.Tensor, krt: torch.Tenso
     return (out, info) if want_info else out
 
 
+VIEW_METHODS = {"pymvg": 0, "naive": 1, "refine": 2}
+
+
+def triangulate_views(pts: torch.Tensor, conf: torch.Tensor, krt: torch.Tensor, *, method: str, conf_thres: float,
+                      ransac_thres: float = 3.0, want_info: bool = False):
+    """KEYPOINT.TRIANGULATION pymvg / naive / refine (vision/triangulation.py:425-441, 99-154, 162-232) for all frames and joints
+    in ONE kernel (et_triangulate_views, float64 arithmetic): the liftings that need only detections, scores and projections.
+    pts (F,V,J,2): image coordinates; conf (F,V,J); krt (F,V,3,4).  `pymvg`: the DLT over the views above `conf_thres`, the
+    threshold lowered in steps of 0.05 until two views remain (`ransac_thres` is not read).  `naive`: every pair of views above
+    `conf_thres` is a hypothesis, the first with the most rays within `ransac_thres` of its two-view point wins and that point is
+    returned.  `refine`: the same search, then the DLT over the winner's inliers when it has more than one.  Returns the (F,J,3)
+    float64 world points -- and, with `want_info`, the (F,J) int32 decision word of include/epipolar_amd.h (views selected, views
+    used, zeros written, threshold steps).  A joint with fewer than two usable views, or no inlier, is (0, 0, 0) and flagged.
+
+    One deviation from the reference, the one `triangulate_epipolar` states: the pair hypotheses of `naive` / `refine` are always
+    enumerated.  The reference draws 100 random ordered pairs per joint; for V <= 8 "all ordered pairs in lexicographic order,
+    cyclically" is one sequence those draws can produce, it visits every pair, and its result is the result of the enumeration
+    (tests/golden/make_triangulation_ransac_golden.py runs the reference on exactly that sequence).  No gradient."""
+    if method not in VIEW_METHODS:
+        raise ValueError("method must be one of %s, got %r" % (", ".join(VIEW_METHODS), method))
+    _require_gpu(pts, "pts")
+    if pts.dim() != 4 or pts.shape[-1] != 2:
+        raise ValueError("pts must be (F,V,J,2), got %s" % (tuple(pts.shape),))
+    f, v, j, _ = pts.shape
+    dev = pts.device
+    _require_f32(pts, "pts", dev)
+    _require_f32(conf, "conf", dev, (f, v, j))
+    _require_f32(krt, "krt", dev, (f, v, 3, 4))
+    out = _empty((f, j, 3), device=dev, dtype=torch.float64)
+    info = torch.empty((f, j), dtype=torch.int32, device=dev) if want_info else None
+    _call("et_triangulate_views", pts, f, v, j, _ptr(pts), _ptr(conf), _ptr(krt), VIEW_METHODS[method], float(conf_thres),
+          float(ransac_thres), _ptr(out), _ptr(info), _stream(pts))
+    return (out, info) if want_info else out
+
+
 def rpsm_workspace_bytes(frames: int, joints: int, first_nbins: int, recur_nbins: int) -> int:
     return int(_lib.load().et_rpsm_workspace_bytes(int(frames), int(joints), int(first_nbins), int(recur_nbins)))
 

@@ -445,6 +445,34 @@ int et_debug_host_triangulate_epipolar(int32_t F, int32_t V, int32_t J, int32_t 
                                        float resize, double conf_thres, double ransac_thres, int32_t dlt, double *out,
                                        int32_t *info);
 
+/* KEYPOINT.TRIANGULATION pymvg / naive / refine (vision/triangulation.py:425-441, 99-154, 162-232): the liftings that need only
+ * detections, scores and projections.  Every (frame, joint) is independent; inputs float32, all arithmetic float64.  One launch.
+ *   pts : (F, V, J, 2) image coordinates ;  conf : (F, V, J) ;  krt : (F, V, 3, 4)
+ *   method : 0 = pymvg, 1 = naive, 2 = refine ;  conf_thres / ransac_thres : cfg.KEYPOINT.CONF_THRES / RANSAC_THRES
+ *   out : (F, J, 3) float64 world points ;  info : (F, J) int32 or NULL
+ * pymvg: t = conf_thres; the views with conf > float32(t), compared in float32, are selected; while at most one is and t >= -1,
+ * t -= 0.05 in float64 (repeated subtraction: the rounding of the sequence is part of the rule); then the DLT over the selected
+ * views.  Fewer than two views at the end (V = 1, NaN scores, scores <= -1): (0, 0, 0) and bit 18 -- the reference fails there.
+ * ransac_thres is not read.
+ * naive: the views with conf > float32(conf_thres); at most one: (0, 0, 0) and bit 18.  Otherwise every pair a < b of selected
+ * views in lexicographic order is a hypothesis (its two-view DLT point p), its inliers are the selected views whose ray through
+ * their detection passes p closer than ransac_thres, and the FIRST hypothesis with the largest count wins: its p, or (0, 0, 0)
+ * and bit 18 when no hypothesis has an inlier.
+ * refine: the same search; a winner with more than one inlier returns the DLT over its inliers, with exactly one its p.
+ * One deviation from the reference: naive and refine there draw 100 random ordered pairs per joint; here every pair is
+ * enumerated.  For V <= 8 the draws "all ordered pairs in lexicographic order, cyclically" are one sequence the reference can
+ * produce, it visits every pair, and its result is the result of the enumeration.
+ *   info bits 0-7  : views selected           bits 8-15 : the views the returned point was computed from (none: 0)
+ *        bit 18    : zeros written            bits 24-30: threshold steps taken (pymvg)
+ * V <= 8, conf_thres finite and <= 2 (at most 61 steps).  No atomics: bit-reproducible. */
+int et_triangulate_views(int32_t F, int32_t V, int32_t J, const float *pts, const float *conf, const float *krt, int32_t method,
+                         double conf_thres, double ransac_thres, double *out, int32_t *info, void *stream);
+
+/* Test hook (HOST pointers, runs on the CPU, no GPU needed): the per-joint routine of et_triangulate_views
+ * (csrc/et_triangulate.h, shared with the kernels) in a serial loop.  Not a CPU fallback of the path. */
+int et_debug_host_triangulate_views(int32_t F, int32_t V, int32_t J, const float *pts, const float *conf, const float *krt,
+                                    int32_t method, double conf_thres, double ransac_thres, double *out, int32_t *info);
+
 /* KEYPOINT.TRIANGULATION rpsm: the recursive pictorial structure model (modeling/pictorial_cuda.py:222-254) for F frames at once,
  * float32 as the reference.  A first stage scores first_nbins^3 candidate positions per joint (a grid of grid_size around
  * center[f]) against every view's heat map and runs max-product over the limbs of the skeleton; recur_depth levels follow, each
