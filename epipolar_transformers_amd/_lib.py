@@ -103,6 +103,12 @@ _SIGNATURES = {
                 [ctypes.c_float, ctypes.c_int32, _P, _P, _P, ctypes.c_size_t, _P]),
     "et_debug_host_rpsm": (ctypes.c_int, [ctypes.c_int32] * 5 + [_P] * 7 + [ctypes.c_float] * 2 + [ctypes.c_double] +
                            [ctypes.c_int32] * 3 + [ctypes.c_float, ctypes.c_int32, _P, _P]),
+    "et_eval_jdr": (ctypes.c_int, [ctypes.c_int32] * 4 + [_P, _P, ctypes.c_double] + [_P] * 5),
+    "et_debug_host_eval_jdr": (ctypes.c_int, [ctypes.c_int32] * 4 + [_P, _P, ctypes.c_double] + [_P] * 4),
+    "et_eval_pck": (ctypes.c_int, [ctypes.c_int32] * 2 + [_P] * 3 + [ctypes.c_int32, _P, ctypes.c_int32] + [_P] * 5),
+    "et_debug_host_eval_pck": (ctypes.c_int, [ctypes.c_int32] * 2 + [_P] * 3 + [ctypes.c_int32, _P, ctypes.c_int32] + [_P] * 4),
+    "et_eval_epe": (ctypes.c_int, [ctypes.c_int32] * 2 + [_P] * 3 + [ctypes.c_double] * 2 + [_P] * 3),
+    "et_debug_host_eval_epe": (ctypes.c_int, [ctypes.c_int32] * 2 + [_P] * 3 + [ctypes.c_double] * 2 + [_P] * 2),
     "et_nchw_to_nhwc": (ctypes.c_int, [ctypes.c_int32] * 4 + [_P, _P, _P]),
     "et_nhwc_to_nchw": (ctypes.c_int, [ctypes.c_int32] * 4 + [_P, _P, _P]),
     "et_debug_host_sample_setup": (ctypes.c_int, [_D, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P]),

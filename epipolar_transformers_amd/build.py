@@ -31,6 +31,7 @@ UNITS = {
     "et_residual_gemm.hip": ["kernels_residual_gemm.inc", "et_wave_reduce.h"],
     "et_triangulate.hip": ["et_triangulate.h", "et_wave_reduce.h"],
     "et_rpsm.hip": ["et_rpsm.h"],
+    "et_metrics.hip": ["et_metrics.h", "et_wave_reduce.h"],
 }
 LIB = os.path.join(PKG, "lib", "libepipolar_amd.so")
 OBJ = os.path.join(PKG, "lib", "obj")

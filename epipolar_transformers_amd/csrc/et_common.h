@@ -27,6 +27,8 @@
 //                                                    pymvg / naive / refine (et_triangulate_views): a lane per joint / the same
 //   et_rpsm.hip           et_rpsm.h                  KEYPOINT.TRIANGULATION rpsm: unary / max-product message / per-frame recursion
 //                                                    kernels, float32, no pairwise table; host + device routine
+//   et_metrics.hip        et_metrics.h               the test-time metrics of Modelbuilder.forward: JDR (block arg-max per map), PCK
+//                                                    counts, EPEmean in float64 with a fixed summation order; host + device routine
 //   et_misc.hip           kernels_misc.inc           sample_locs, residual epilogue, NCHW <-> NHWC, ABI version / errors
 //   et_wave_reduce.h                                 DPP wave reductions (wave_all_sum / max / min): general, tile, GEMM units
 //   et_split_f16.h                                   fp32 -> two fp16 halves for the matrix cores (tile units)

@@ -33,6 +33,10 @@ from .config import get_cfg
 from .triangulate import mpjpe, triangulate_dlt
 
 
+# DATASETS.H36M.MAPPING (model.py:268-274): the 17 H36M joints among the 20 channels of the heads trained with it
+H36M_MAPPING = (0, 1, 2, 3, 4, 5, 6, 7, 9, 11, 12, 14, 15, 16, 17, 18, 19)
+
+
 def ring_sources(num_frames: int, num_views: int, device=None) -> torch.Tensor:
     """Index of the source view of every view of a frame-major (frames * views) batch: view v+1 of the same frame
     (the pairing of the synthetic rig; H36M uses `neighbor_cameras`, vision/multiview.py:59-83 -- pass that instead)."""
@@ -232,6 +236,29 @@ class MultiViewPoseModel(nn.Module):
         return triangulate_dlt(pts, KRT.to(batch_locs.device).view(f, num_views, 3, 4), batch_scos.view(f, num_views, j),
                                conf_thres=float(getattr(cfg.KEYPOINT, "CONF_THRES", 0.05)))
 
+    # ------------------------------------------------------------------------------------------ test-time 2-D metrics
+    def metrics_2d(self, inputs: dict, heat, target_heat, batch_locs, visibility, metric_dict: dict, out: dict):
+        """The `cfg.TEST.PCK` block of Modelbuilder.forward (model.py:372-404; PCK defaults to True) on the device, into
+        `metric_dict` / `out`: JDR of the predicted against the target heat maps (ops.eval_jdr; not under EPIPOLAR.MULTITEST, which
+        keeps no maps) and, with the batch's `points-2d`, calculate_err -- the reference's DOTEST branch, its default -- on the
+        detections (ops.eval_pck): PCK@<th> for cfg.TEST.THRESHOLDS, err_joints / total_joints for cfg.TEST.MAX_TH.  The values
+        are device tensors; nothing is copied to the host."""
+        test = self.cfg.get("TEST") if hasattr(self.cfg, "get") else None
+        if not getattr(test, "PCK", True):
+            return
+        if heat is not None and target_heat is not None:
+            dev = heat[0].device
+            _, acc = ops.eval_jdr(heat[0].detach().to(torch.float32).contiguous(), target_heat.to(dev, torch.float32).contiguous())
+            metric_dict["JDR"], out["jdr_per_joint"] = acc[0], acc[1:]
+        if inputs.get("points-2d") is not None:
+            thresholds = tuple(getattr(test, "THRESHOLDS", (1, 2, 5, 10, 20, 30, 40, 50, 60, 80, 100)))
+            locs = batch_locs.detach().to(torch.float32).contiguous()
+            gt = inputs["points-2d"][..., :2].to(locs.device, torch.float64).contiguous()
+            pck, out["err_joints"], out["total_joints"] = ops.eval_pck(locs, gt, vis=visibility, thresholds=thresholds,
+                                                                       max_threshold=getattr(test, "MAX_TH", 20))
+            for i, th in enumerate(thresholds):
+                metric_dict["PCK@" + str(th)] = pck[i]
+
     # ------------------------------------------------------------------------------------------ Modelbuilder.forward
     def forward(self, inputs: dict, is_train: bool = True):
         """The multiview_keypoint branch of Modelbuilder.forward (model.py:160-302).  `inputs` holds the reference's
@@ -241,7 +268,23 @@ class MultiViewPoseModel(nn.Module):
         `crop_center` (F*V,2), `crop_scale` (F*V,2) or (F*V,), `center` (F,3), `limb_length` (F,J-1) or (J-1,) and optionally
         `first_limb_length`, `parent` -- the reference takes centre and limb lengths from the first frame's ground truth, here
         the caller supplies them per frame.  Returns (loss_dict, metric_dict) in training, (loss_dict, metric_dict, out) otherwise, as the reference does
-        (model.py:478-493)."""
+        (model.py:478-493).
+
+        EPIPOLAR_AMD.EVAL_METRICS (default off: everything above is all there is) adds, in evaluation, the rest of the reference's
+        test-time branch, computed on the device with no copy to the host:
+          * DATASETS.H36M.MAPPING (model.py:268-274), when the key is present and true (absent counts as false): the predicted heat
+            maps, the target `heatmap`, the detections, their scores and `visibility` are reduced to the 17 channels H36M_MAPPING
+            before the lift and before any metric; a head with other than 20 channels is a ValueError.  The reference also tests
+            `'h36m' in cfg.OUTPUT_DIR`, its switch between data sets; this model IS the H36M task, so that test is dropped.
+          * metric_dict["EPEmean_global"] and out["epe_per_joint"] (F,J) from ops.eval_epe (EPEmean, model.py:339-346), given a lift
+            and `points-3d`; `unit` = inputs.get("unit") or 1, a host number; the clamp is cfg.TEST.EPEMEAN_MAX_DIST (150 when
+            absent); visibility is that of each frame's first view, like `points-3d`.  "MPJPE" stays.  The reference drops the
+            key when the value is NaN (:345), a test that needs the value on the host: here the key is always written and a NaN
+            stays a NaN.
+          * unless cfg.TEST.PCK is false (absent counts as true, the reference's default): `metrics_2d` -- "JDR" and
+            out["jdr_per_joint"] given a target `heatmap`, "PCK@<th>", out["err_joints"] and out["total_joints"] given `points-2d`
+            (M,J,>=2; the J joints that remain after the mapping).
+        The per-action and per-joint-name keys (MPJPE@<action>, JDR@<name>) need the data set's name tables and are not written."""
         cfg = self.cfg
         img = inputs["img"]
         KRT = inputs["KRT"].to(torch.float32)                               # model.py:183-185
@@ -265,6 +308,24 @@ class MultiViewPoseModel(nn.Module):
                 res = self.reference(img, [other_features, other_KRT, None, KRT, camera, other_camera, inputs["other_img"]])  # model.py:246
             _, heat, batch_locs, batch_scos, corr_pos, depths, _, _ = res
         loss_dict, metric_dict, out = {}, {}, {}
+        from .config import amd_knob
+
+        evaluate = not is_train and bool(amd_knob(cfg, "EVAL_METRICS", False))
+        target_heat, visibility = inputs.get("heatmap"), inputs.get("visibility")
+        if evaluate:
+            m = batch_locs.shape[0]
+            if visibility is not None:
+                visibility = visibility.to(batch_locs.device, torch.float32).reshape(m, -1)            # model.py:181
+            h36m = cfg.DATASETS.get("H36M") if hasattr(cfg.DATASETS, "get") else None
+            if h36m is not None and h36m.get("MAPPING", False):                                          # model.py:268-274
+                if batch_locs.shape[1] != 20:
+                    raise ValueError("DATASETS.H36M.MAPPING takes the 17 H36M joints out of a 20-channel head; this head has %d "
+                                     "channels" % batch_locs.shape[1])
+                keep = torch.tensor(H36M_MAPPING, device=batch_locs.device)
+                take = lambda t: None if t is None else t.index_select(1, keep.to(t.device))
+                if heat is not None:
+                    heat = [take(heat[0])] + list(heat[1:])
+                target_heat, batch_locs, batch_scos, visibility = take(target_heat), take(batch_locs), take(batch_scos), take(visibility)
         if is_train and inputs.get("heatmap") is not None:
             vis = inputs.get("visibility")
             vis = torch.ones(heat[0].shape[:2], device=heat[0].device) if vis is None else vis.to(torch.float32)
@@ -280,6 +341,14 @@ class MultiViewPoseModel(nn.Module):
             if inputs.get("points-3d") is not None:
                 gt = inputs["points-3d"].to(pred.device).view(-1, views, pred.shape[1], 3)[:, 0]
                 metric_dict["MPJPE"] = mpjpe(pred, gt)                      # metrics3d.py:5-46
+                if evaluate:                                                # model.py:339-346
+                    test = cfg.get("TEST") if hasattr(cfg, "get") else None
+                    vis = None if visibility is None else visibility.view(-1, views, visibility.shape[1])[:, 0].contiguous()
+                    metric_dict["EPEmean_global"], out["epe_per_joint"] = ops.eval_epe(
+                        pred.to(torch.float64).contiguous(), gt.to(torch.float64).contiguous(), vis=vis,
+                        unit=float(inputs.get("unit") or 1), max_dist=float(getattr(test, "EPEMEAN_MAX_DIST", 150)))
+        if evaluate:
+            self.metrics_2d(inputs, heat, target_heat, batch_locs, visibility, metric_dict, out)
         # model.py:478-493: several losses are summed into 'loss', a single one is RENAMED to 'loss'; training returns
         # (loss_dict, metric_dict), evaluation (loss_dict, metric_dict, out) with the empty entries of `out` dropped
         if len(loss_dict) > 1:

@@ -884,6 +884,102 @@ def triangulate_views(pts: torch.Tensor, conf: torch.Tensor, krt: torch.Tensor, 
     return (out, info) if want_info else out
 
 
+def _optional_vis(vis, shape, device):
+    if vis is not None:
+        _require_f32(vis, "vis", device, shape)
+    return vis
+
+
+def eval_jdr(pred: torch.Tensor, target: torch.Tensor, thr: float = 0.5, want_xy: bool = False):
+    """JDR (modeling/metrics/metrics2d.py:294-324, hm_type 'gaussian') of predicted against target heat maps, both (N,J,H,W)
+    float32, on the device (et_eval_jdr: one block per map finds both first maxima, a second small launch counts).  Returns
+    `dists` (J,N) float64 -- the reference's layout: -1 where the target's maximum lies at x <= 1 or y <= 1, else the norm of
+    (pred - target) / (H/10, W/10), x over the HEIGHT term as the reference has it -- and `acc` (J+1,) float64: acc[1 + j] the
+    share of joint j's counted distances below `thr` (-1: none counts), acc[0] their average in joint order (NaN when no joint
+    counts; the reference raises there).  With `want_xy` also get_max_preds' masked integer coordinates of both stacks,
+    (N,J,2) float32.  Bit-equal to the reference; no synchronisation.  2 <= H, W and H * W <= 16384.  No gradient."""
+    _require_gpu(pred, "pred")
+    if pred.dim() != 4:
+        raise ValueError("pred must be (N,J,H,W), got %s" % (tuple(pred.shape),))
+    n, j, h, w = pred.shape
+    dev = pred.device
+    _require_f32(pred, "pred", dev)
+    _require_f32(target, "target", dev, (n, j, h, w))
+    dists = _empty((j, n), device=dev, dtype=torch.float64)
+    acc = _empty((j + 1,), device=dev, dtype=torch.float64)
+    pred_xy = _empty((n, j, 2), device=dev) if want_xy else None
+    target_xy = _empty((n, j, 2), device=dev) if want_xy else None
+    _call("et_eval_jdr", pred, n, j, h, w, _ptr(pred), _ptr(target), float(thr), _ptr(dists), _ptr(acc), _ptr(pred_xy), _ptr(target_xy),
+          _stream(pred))
+    return (dists, acc, pred_xy, target_xy) if want_xy else (dists, acc)
+
+
+_MARKS = {}     # (device, values) -> float64 device array: the thresholds / curve points of eval_pck, filled on the host once
+
+
+def _marks(values, device) -> torch.Tensor:
+    host = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    key = (str(device), host.tobytes())
+    if key not in _MARKS:
+        _MARKS[key] = torch.from_numpy(host).to(device)
+        torch.cuda.current_stream(device).synchronize()      # once per set of values: later calls on any stream find it uploaded
+    return _MARKS[key]
+
+
+def eval_pck(locs: torch.Tensor, gt: torch.Tensor, vis: torch.Tensor = None, *, thresholds=(1, 2, 5, 10, 20, 30, 40, 50, 60, 80, 100),
+             max_threshold=20):
+    """calculate_err (modeling/metrics/metrics2d.py:199-235; its PCKs are calc_pck's) on the device (et_eval_pck).  locs (N,J,2)
+    float32 detections, gt (N,J,2) float64, vis (N,J) float32 or None (all visible; an item counts when vis != 0).  Returns `pck`
+    (T,) float64: count(err < th) * 100 / count over the whole batch for every th of `thresholds` (cfg.TEST.THRESHOLDS; NaN when
+    nothing counts), `err_joints` (N,M) float64: per sample the count of err < c over the M = int(max_threshold) points c of
+    np.linspace(0, max_threshold, num=int(max_threshold)) (cfg.TEST.MAX_TH; made with NumPy, so its bits are the reference's), and
+    `total_joints` (N,1) float64.  The error is |x - x_gt| -- x ONLY: the reference's `detected_points[:1, j]` takes the first row
+    of its (2,J) array.  Bit-equal to the reference; no synchronisation (the thresholds are uploaded once and kept).  No gradient."""
+    _require_gpu(locs, "locs")
+    if locs.dim() != 3 or locs.shape[-1] != 2:
+        raise ValueError("locs must be (N,J,2), got %s" % (tuple(locs.shape),))
+    n, j, _ = locs.shape
+    dev = locs.device
+    _require_f32(locs, "locs", dev)
+    _require_gpu(gt, "gt", torch.float64)
+    if gt.device != dev or not gt.is_contiguous() or tuple(gt.shape) != (n, j, 2):
+        raise ValueError("gt must be a contiguous float64 tensor of shape %s on %s, got %s on %s" % ((n, j, 2), dev, tuple(gt.shape), gt.device))
+    _optional_vis(vis, (n, j), dev)
+    th = _marks(thresholds, dev)
+    curve = _marks(np.linspace(0, max_threshold, num=int(max_threshold)), dev)
+    t, m = th.numel(), curve.numel()
+    pck = _empty((t,), device=dev, dtype=torch.float64)
+    err_joints = _empty((n, m), device=dev, dtype=torch.float64)
+    total_joints = _empty((n, 1), device=dev, dtype=torch.float64)
+    _call("et_eval_pck", locs, n, j, _ptr(locs), _ptr(gt), _ptr(vis), t, _ptr(th if t else None), m, _ptr(curve if m else None),
+          _ptr(pck if t else None), _ptr(err_joints if m else None), _ptr(total_joints), _stream(locs))
+    return pck, err_joints, total_joints
+
+
+def eval_epe(pred: torch.Tensor, gt: torch.Tensor, vis: torch.Tensor = None, *, unit: float = 1.0, max_dist: float = 150.0):
+    """EPEmean (modeling/metrics/metrics3d.py:5-46) in float64 on the device (et_eval_epe).  pred, gt (F,J,3) float64, vis (F,J)
+    float32 or None; `unit` and `max_dist` (cfg.TEST.EPEMEAN_MAX_DIST) are host numbers.  err = sqrt((dx^2 + dy^2) + dz^2) * unit,
+    replaced by max_dist where it exceeds it.  Returns `mean`, a 0-d float64 tensor -- over all F * J items: visibility does not
+    enter it, as in the reference -- summed in a fixed order, and `per_joint` (F,J) float64: err with the items of vis == 0 set
+    to 0 (the reference returns row 0 of it), bit-equal to the reference.  No synchronisation.  No gradient."""
+    _require_gpu(pred, "pred", torch.float64)
+    if pred.dim() != 3 or pred.shape[-1] != 3:
+        raise ValueError("pred must be (F,J,3), got %s" % (tuple(pred.shape),))
+    f, j, _ = pred.shape
+    dev = pred.device
+    _require_gpu(gt, "gt", torch.float64)
+    for t, name in ((pred, "pred"), (gt, "gt")):
+        if t.device != dev or not t.is_contiguous() or tuple(t.shape) != (f, j, 3):
+            raise ValueError("%s must be a contiguous float64 tensor of shape %s on %s, got %s on %s" % (
+                name, (f, j, 3), dev, tuple(t.shape), t.device))
+    _optional_vis(vis, (f, j), dev)
+    mean = _empty((), device=dev, dtype=torch.float64)
+    per_joint = _empty((f, j), device=dev, dtype=torch.float64)
+    _call("et_eval_epe", pred, f, j, _ptr(pred), _ptr(gt), _ptr(vis), float(unit), float(max_dist), _ptr(mean), _ptr(per_joint),
+          _stream(pred))
+    return mean, per_joint
+
+
 def rpsm_workspace_bytes(frames: int, joints: int, first_nbins: int, recur_nbins: int) -> int:
     return int(_lib.load().et_rpsm_workspace_bytes(int(frames), int(joints), int(first_nbins), int(recur_nbins)))
 

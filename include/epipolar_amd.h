@@ -506,6 +506,57 @@ int et_debug_host_rpsm(int32_t F, int32_t V, int32_t J, int32_t H, int32_t W, co
                        const int32_t *parent, float image_w, float image_h, double grid_size, int32_t first_nbins,
                        int32_t recur_nbins, int32_t recur_depth, float tolerance, int32_t align_corners, float *out, int32_t *path);
 
+/* The evaluation metrics of Modelbuilder.forward's test-time branch (modeling/model.py:339-351, 372-404), on the device: the
+ * reference copies both heat-map stacks to the host and walks N * J items in Python.  Every value below is a count of exact
+ * decisions or a float64 expression of the reference's operands in the reference's order, each operation rounded once (no FMA
+ * contraction), so the results equal the reference's to the bit; the sums run in a fixed order without atomics, so they are
+ * bit-reproducible.  Inputs are finite by contract: the result for a map or a point that holds a NaN is unspecified.
+ *
+ * et_eval_jdr: JDR (modeling/metrics/metrics2d.py:294-324, hm_type 'gaussian') with get_max_preds (basic_batch.py:67-95),
+ * calc_dists (:269-281) and dist_acc (:284-291).
+ *   pred, target : (N, J, H, W) float32, predicted and target heat maps ;  thr : the reference's 0.5
+ *   dists : (J, N) float64, the reference's own layout ;  acc : (J + 1) float64
+ *   pred_xy, target_xy : (N, J, 2) float32 or NULL -- what get_max_preds returns
+ * Per map the FIRST maximum (value, then lowest flat index, as np.argmax; -0.0 and +0.0 tie): x = idx % W, y = idx / W, both
+ * set to 0 unless the maximum is > 0.  dists[j][n] = -1 unless the target's x > 1 and y > 1; otherwise the float64 norm of
+ * (pred - target) / normalize with normalize = (H / 10, W / 10) applied to (x, y) IN THAT ORDER -- the reference divides x by
+ * the height term, and so does this.  acc[1 + j] = (dists[j] < thr among dists[j] != -1) / their number, or -1 when no sample
+ * counts; acc[0] = the sum of the non-negative acc[1 + j] in joint order / their number -- NaN when no joint counts (the
+ * reference divides zero by zero there and raises).  2 <= H, 2 <= W, H * W <= 16384. */
+int et_eval_jdr(int32_t N, int32_t J, int32_t H, int32_t W, const float *pred, const float *target, double thr, double *dists,
+                double *acc, float *pred_xy, float *target_xy, void *stream);
+
+/* et_eval_pck: calculate_err (metrics2d.py:199-235), whose PCKs are calc_pck's (:238-265).
+ *   locs : (N, J, 2) float32 detections ;  gt : (N, J, 2) float64 ;  vis : (N, J) float32 or NULL (all visible); an item counts
+ *   when vis != 0
+ *   thresholds : T float64 (cfg.TEST.THRESHOLDS) ;  curve : M float64 (np.linspace(0, MAX_TH, num=int(MAX_TH)))
+ *   pck : T float64 ;  err_joints : (N, M) float64 ;  total_joints : (N) float64
+ * The error of a counted item is |double(locs.x) - gt.x| -- x ONLY: the reference's `detected_points[:1, j]` selects the first
+ * row of its (2, J) array, and this reproduces it.  pck[t] = count(err < thresholds[t]) * 100.0 / count over the whole batch (NaN
+ * when nothing counts); err_joints[n][m] = count over sample n of err < curve[m]; total_joints[n] = counted items of sample n.
+ * T == 0 and M == 0 are valid and write nothing of their array (which may then be NULL). */
+int et_eval_pck(int32_t N, int32_t J, const float *locs, const double *gt, const float *vis, int32_t T, const double *thresholds,
+                int32_t M, const double *curve, double *pck, double *err_joints, double *total_joints, void *stream);
+
+/* et_eval_epe: EPEmean (modeling/metrics/metrics3d.py:5-46) in float64.
+ *   pred, gt : (F, J, 3) float64 ;  vis : (F, J) float32 or NULL ;  unit, max_dist : the batch's unit, cfg.TEST.EPEMEAN_MAX_DIST
+ *   mean : 1 float64 ;  per_joint : (F, J) float64 (the reference returns row 0 of it)
+ * err = sqrt((dx^2 + dy^2) + dz^2) * unit, replaced by max_dist where it exceeds it; mean = the mean over all F * J items --
+ * visibility does not enter it, as in the reference -- summed in a fixed order (256 strided partial sums, then a pairwise tree);
+ * per_joint = err with the items of vis == 0 set to 0. */
+int et_eval_epe(int32_t F, int32_t J, const double *pred, const double *gt, const float *vis, double unit, double max_dist,
+                double *mean, double *per_joint, void *stream);
+
+/* Test hooks (HOST pointers, run on the CPU, no GPU needed): the per-item routines of the three calls above (csrc/et_metrics.h,
+ * shared with the kernels) in serial loops, the mean in the kernel's summation order.  Not a CPU fallback of the path. */
+int et_debug_host_eval_jdr(int32_t N, int32_t J, int32_t H, int32_t W, const float *pred, const float *target, double thr,
+                           double *dists, double *acc, float *pred_xy, float *target_xy);
+int et_debug_host_eval_pck(int32_t N, int32_t J, const float *locs, const double *gt, const float *vis, int32_t T,
+                           const double *thresholds, int32_t M, const double *curve, double *pck, double *err_joints,
+                           double *total_joints);
+int et_debug_host_eval_epe(int32_t F, int32_t J, const double *pred, const double *gt, const float *vis, double unit, double max_dist,
+                           double *mean, double *per_joint);
+
 /* Layout converters between the reference's NCHW and the kernels' NHWC. */
 int et_nchw_to_nhwc(int32_t N, int32_t C, int32_t H, int32_t W, const float *src, float *dst, void *stream);
 int et_nhwc_to_nchw(int32_t N, int32_t C, int32_t H, int32_t W, const float *src, float *dst, void *stream);
