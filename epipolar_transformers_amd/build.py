@@ -27,7 +27,7 @@ UNITS = {
     "et_backward.hip": ["kernels_sample_table.inc", "kernels_pixel_phases.inc", "kernels_backward.inc"],
     "et_backward_tile.hip": ["kernels_tile_order.inc", "kernels_tile_common.inc", "kernels_backward_tile.inc", "kernels_backward_det.inc",
                              "et_tile_host.h", "et_tile_layout.h", "et_wave_reduce.h", "et_split_f16.h", "et_lds_layout.h"],
-    "et_misc.hip": ["kernels_misc.inc"],
+    "et_misc.hip": ["kernels_misc.inc", "et_peaks.h"],
     "et_residual_gemm.hip": ["kernels_residual_gemm.inc", "et_wave_reduce.h"],
     "et_triangulate.hip": ["et_triangulate.h", "et_wave_reduce.h"],
     "et_rpsm.hip": ["et_rpsm.h"],

@@ -30,6 +30,7 @@
 //   et_metrics.hip        et_metrics.h               the test-time metrics of Modelbuilder.forward: JDR (block arg-max per map), PCK
 //                                                    counts, EPEmean in float64 with a fixed summation order; host + device routine
 //   et_misc.hip           kernels_misc.inc           sample_locs, residual epilogue, NCHW <-> NHWC, ABI version / errors
+//                         et_peaks.h                 the head's peak finder for one map (et_heatmap_peaks); host + device routine
 //   et_wave_reduce.h                                 DPP wave reductions (wave_all_sum / max / min): general, tile, GEMM units
 //   et_split_f16.h                                   fp32 -> two fp16 halves for the matrix cores (tile units)
 //   epipolar_geometry.h                              bit-faithful float32 geometry (segment, sample set-up), host+device

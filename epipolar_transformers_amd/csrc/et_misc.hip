@@ -1,10 +1,23 @@
 // libepipolar_amd.so: ABI version / error text, sample_locs, residual epilogue, layout converters, host test hook.
 #include "et_common.h"
+#include "et_peaks.h"
 
 thread_local char et_g_err[512] = "";
 
 namespace {
-#include "kernels_misc.inc"      // sample_locs_kernel, residual_epilogue_kernel, transpose_kernel
+#include "kernels_misc.inc"      // sample_locs_kernel, residual_epilogue_kernel, transpose_kernel, heatmap_peaks_kernel
+
+// the argument checks et_heatmap_peaks and its host hook share
+int check_peaks(const char *what, int64_t num_maps, int32_t H, int32_t W, const float *heatmaps, float radius, const float *locs,
+                const float *scores)
+{
+    if (num_maps <= 0 || num_maps > 0x7fffffffLL || H < 2 || W < 2) return fail("%s: bad sizes (%lld maps of %d x %d)", what, (long long)num_maps, H, W);
+    if ((long long)H * W > 0x7ffffffeLL) return fail("%s: map %d x %d too large", what, H, W);
+    // int(radius + 0.5) >= 1 (the ramp's step divides by it); the upper end keeps the window's pixel arithmetic finite
+    if (!(radius > 0.f) || !(radius <= 4096.f) || (int)(radius + 0.5f) < 1) return fail("%s: radius %g outside [0.5, 4096]", what, radius);
+    if (!heatmaps || !locs || !scores) return fail("%s: NULL pointer", what);
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -96,12 +109,20 @@ int et_debug_atomic_probe(float *dst, int64_t rows, int32_t blocks, int32_t iter
 int et_heatmap_peaks(int64_t num_maps, int32_t H, int32_t W, const float *heatmaps, float radius, float downsample,
                      float threshold, int32_t legacy_floor_division, float *locs, float *scores, void *stream)
 {
-    if (num_maps <= 0 || num_maps > 0x7fffffffLL || H < 2 || W < 2) return fail("et_heatmap_peaks: bad sizes");
-    if (!(radius > 0.f) || (int)(radius + 0.5f) < 1) return fail("et_heatmap_peaks: radius %g", radius);
-    if (!heatmaps || !locs || !scores) return fail("et_heatmap_peaks: NULL pointer");
-    hipLaunchKernelGGL(heatmap_peaks_kernel, dim3((unsigned)num_maps), dim3(256), 0, (hipStream_t)stream, heatmaps, H, W,
+    if (int e = check_peaks("et_heatmap_peaks", num_maps, H, W, heatmaps, radius, locs, scores)) return e;
+    hipLaunchKernelGGL(heatmap_peaks_kernel, dim3((unsigned)num_maps), dim3(et_peaks::kThreads), 0, (hipStream_t)stream, heatmaps, H, W,
                        radius, downsample, threshold, legacy_floor_division, locs, scores);
     return check_launch("et_heatmap_peaks");
+}
+
+int et_debug_host_heatmap_peaks(int64_t num_maps, int32_t H, int32_t W, const float *heatmaps, float radius, float downsample,
+                                float threshold, int32_t legacy_floor_division, float *locs, float *scores)
+{
+    if (int e = check_peaks("et_debug_host_heatmap_peaks", num_maps, H, W, heatmaps, radius, locs, scores)) return e;
+    for (int64_t m = 0; m < num_maps; ++m)
+        et_peaks::host_peak(heatmaps + (size_t)m * H * W, H, W, radius, downsample, threshold, legacy_floor_division, locs + 2 * m,
+                            scores + m);
+    return 0;
 }
 
 }  // extern "C"

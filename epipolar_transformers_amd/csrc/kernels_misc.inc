@@ -84,23 +84,25 @@ __global__ __launch_bounds__(256) void transpose_kernel(int rows, int cols, cons
 //      (align_corners = False, zero padding) do for the box [index -+ radius] normalised with -1 + 2 x / (L - 1)
 //   3. values <= threshold dropped, centre of mass with the ramp arange(-radius, radius, radius / r) + index,
 //      then pix2coord (x * downsample + downsample / 2 - 0.5).
+// The arithmetic of one map is et_peaks.h's (shared with the host hook); here: the block's reduction layout.
 // ----------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void heatmap_peaks_kernel(const float *__restrict__ heat, int H, int W, float radius,
-                                                             float downsample, float threshold, int legacy_floor,
-                                                             float *__restrict__ locs, float *__restrict__ scores)
+__global__ __launch_bounds__(et_peaks::kThreads) void heatmap_peaks_kernel(const float *__restrict__ heat, int H, int W, float radius,
+                                                                            float downsample, float threshold, int legacy_floor,
+                                                                            float *__restrict__ locs, float *__restrict__ scores)
 {
-    __shared__ float s_val[256];
-    __shared__ int s_idx[256];
+    constexpr int kThreads = et_peaks::kThreads;
+    __shared__ float s_val[kThreads];
+    __shared__ int s_idx[kThreads];
     __shared__ float s_acc[3][4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float *hm = heat + (size_t)blockIdx.x * H * W;
     const int HW = H * W;
-    // ---- 1. arg-max (value, then lowest index) ----
+    // ---- 1. arg-max (NaN above every value, then the value, then the lowest index: et_peaks.h) ----
     float best = -__builtin_huge_valf();
-    int bidx = 0x7fffffff;
-    for (int i = tid; i < HW; i += 256) {
+    int bidx = et_peaks::kNoCandidate;
+    for (int i = tid; i < HW; i += kThreads) {
         const float v = hm[i];
-        if (v > best) {
+        if (et_peaks::takes_over(v, best)) {
             best = v;
             bidx = i;
         }
@@ -108,11 +110,11 @@ __global__ __launch_bounds__(256) void heatmap_peaks_kernel(const float *__restr
     s_val[tid] = best;
     s_idx[tid] = bidx;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
+    for (int s = kThreads / 2; s > 0; s >>= 1) {
         if (tid < s) {
             const float v = s_val[tid + s];
             const int i = s_idx[tid + s];
-            if (v > s_val[tid] || (v == s_val[tid] && i < s_idx[tid])) {
+            if (et_peaks::outranks(v, i, s_val[tid], s_idx[tid])) {
                 s_val[tid] = v;
                 s_idx[tid] = i;
             }
@@ -120,34 +122,15 @@ __global__ __launch_bounds__(256) void heatmap_peaks_kernel(const float *__restr
         __syncthreads();
     }
     const float score = s_val[0];
-    const int index = s_idx[0];
-    const float index_w = (float)(index % W);
-    const float index_h = legacy_floor ? (float)(index / W) : (float)index / (float)W;
     // ---- 2. / 3. the resampled window ----
-    auto norm = [](float x, int L) { return -1.f + 2.f * x / (float)(L - 1); };
-    const float x0 = norm(index_w - radius, W), x1 = norm(index_w + radius, W);
-    const float y0 = norm(index_h - radius, H), y1 = norm(index_h + radius, H);
-    const float t00 = (x1 - x0) / 2.f, t02 = (x1 + x0) / 2.f, t11 = (y1 - y0) / 2.f, t12 = (y1 + y0) / 2.f;
-    const int ir = (int)(radius + 0.5f), side = 2 * ir + 1;
-    const float rstep = radius * 1.0f / (float)ir;
+    const et_peaks::Window win = et_peaks::make_window(et_peaks::resolve_index(s_idx[0]), H, W, radius, threshold, legacy_floor);
     float sum = 0.f, sx = 0.f, sy = 0.f;
-    for (int e = tid; e < side * side; e += 256) {
-        const int iy = e / side, ix = e - iy * side;
-        // affine_grid, align_corners = False: output coordinate (2 i + 1) / side - 1
-        const float gx = t00 * ((2.f * ix + 1.f) / (float)side - 1.f) + t02;
-        const float gy = t11 * ((2.f * iy + 1.f) / (float)side - 1.f) + t12;
-        // grid_sample, align_corners = False
-        const float px = ((gx + 1.f) * (float)W - 1.f) / 2.f, py = ((gy + 1.f) * (float)H - 1.f) / 2.f;
-        const float fx = floorf(px), fy = floorf(py);
-        const float wx = px - fx, wy = py - fy;
-        const int x_ = (int)fx, y_ = (int)fy;
-        auto at = [&](int yy, int xx) { return ((unsigned)xx < (unsigned)W && (unsigned)yy < (unsigned)H) ? hm[yy * W + xx] : 0.f; };
-        float v = at(y_, x_) * (1.f - wx) * (1.f - wy) + at(y_, x_ + 1) * wx * (1.f - wy) +
-                  at(y_ + 1, x_) * (1.f - wx) * wy + at(y_ + 1, x_ + 1) * wx * wy;
-        v = v > threshold ? v : 0.f;                                     // F.threshold
+    for (int e = tid; e < win.side * win.side; e += kThreads) {
+        float rx, ry;
+        const float v = et_peaks::window_sample(hm, H, W, win, e, rx, ry);
         sum += v;
-        sx += v * (-radius + rstep * (float)ix);                         // torch.arange(-radius, radius + 1e-4, radius / r)
-        sy += v * (-radius + rstep * (float)iy);
+        sx += v * rx;
+        sy += v * ry;
     }
     for (int o = 32; o >= 1; o >>= 1) {
         sum += __shfl_xor(sum, o);
@@ -161,11 +144,11 @@ __global__ __launch_bounds__(256) void heatmap_peaks_kernel(const float *__restr
     }
     __syncthreads();
     if (tid == 0) {
-        const float tot = (s_acc[0][0] + s_acc[0][1]) + (s_acc[0][2] + s_acc[0][3]) + 2.220446049250313e-16f;   // np.finfo(float).eps
-        const float mx = ((s_acc[1][0] + s_acc[1][1]) + (s_acc[1][2] + s_acc[1][3])) / tot + index_w;
-        const float my = ((s_acc[2][0] + s_acc[2][1]) + (s_acc[2][2] + s_acc[2][3])) / tot + index_h;
-        locs[(size_t)blockIdx.x * 2] = mx * downsample + downsample / 2.0f - 0.5f;       // pix2coord, multiview.py:154-157
-        locs[(size_t)blockIdx.x * 2 + 1] = my * downsample + downsample / 2.0f - 0.5f;
+        float x, y;
+        et_peaks::finish((s_acc[0][0] + s_acc[0][1]) + (s_acc[0][2] + s_acc[0][3]), (s_acc[1][0] + s_acc[1][1]) + (s_acc[1][2] + s_acc[1][3]),
+                         (s_acc[2][0] + s_acc[2][1]) + (s_acc[2][2] + s_acc[2][3]), win, downsample, x, y);
+        locs[(size_t)blockIdx.x * 2] = x;
+        locs[(size_t)blockIdx.x * 2 + 1] = y;
         scores[blockIdx.x] = score;
     }
 }

@@ -409,9 +409,19 @@ int et_epipolar_forward_fused(const EtLayerDesc *desc, const float *xs, const fl
  *   radius   : cfg.KEYPOINT.SIGMA ;  downsample : cfg.BACKBONE.DOWNSAMPLE ;  threshold : 1e-6 in the reference
  *   legacy_floor_division : index / W as integer division (torch < 1.5, what the authors trained with) instead of
  *                           the true division the torch of this image performs
- *   locs     : (num_maps, 2) image coordinates (x, y) ;  scores : (num_maps) the maximum of each map */
+ *   locs     : (num_maps, 2) image coordinates (x, y) ;  scores : (num_maps) the maximum of each map
+ * H, W >= 2 and 0.5 <= radius <= 4096 (int(radius + 0.5) >= 1), else an error.
+ * Non-finite maps, as torch.max / F.grid_sample / F.threshold treat them: a NaN ranks above every value and the first one wins,
+ * so a map that holds a NaN has score NaN and -- the NaN lies in its own window and a sample is dropped only when it is
+ * <= threshold -- NaN coordinates; a +inf cell gives score +inf and NaN coordinates (inf / inf).  A map of -inf alone has no
+ * candidate: index 0, score -inf, and the location of cell 0 or NaN (its window holds -inf * weight, and a weight may be zero);
+ * never a value outside the image.
+ * et_debug_host_heatmap_peaks: HOST test hook, no GPU -- the kernel's per-map routine (csrc/et_peaks.h) in a serial loop, its
+ * sums taken in the kernel's order; host pointers. */
 int et_heatmap_peaks(int64_t num_maps, int32_t H, int32_t W, const float *heatmaps, float radius, float downsample,
                      float threshold, int32_t legacy_floor_division, float *locs, float *scores, void *stream);
+int et_debug_host_heatmap_peaks(int64_t num_maps, int32_t H, int32_t W, const float *heatmaps, float radius, float downsample,
+                                float threshold, int32_t legacy_floor_division, float *locs, float *scores);
 
 /* KEYPOINT.TRIANGULATION epipolar / epipolar_dlt: triangulate_epipolar (vision/triangulation.py:234-348), the lifting that
  * consumes the layer's corr_pos.  Every (frame, joint) is independent; inputs float32, all arithmetic float64.  One launch.
