@@ -30,6 +30,9 @@ ET_GENERAL_PRIOR_MUL = 2
 ET_GENERAL_COSINE = 4
 ET_GENERAL_ATTENTION_MAX = 8
 ET_GENERAL_SIM_PRIOR = 16
+ET_LOSS_JOINT = 0
+ET_LOSS_SMOOTHMSE = 1
+ET_LOSS_MSE = 2
 
 
 class EpipolarAmdError(RuntimeError):
@@ -111,6 +114,12 @@ _SIGNATURES = {
     "et_debug_host_eval_pck": (ctypes.c_int, [ctypes.c_int32] * 2 + [_P] * 3 + [ctypes.c_int32, _P, ctypes.c_int32] + [_P] * 4),
     "et_eval_epe": (ctypes.c_int, [ctypes.c_int32] * 2 + [_P] * 3 + [ctypes.c_double] * 2 + [_P] * 3),
     "et_debug_host_eval_epe": (ctypes.c_int, [ctypes.c_int32] * 2 + [_P] * 3 + [ctypes.c_double] * 2 + [_P] * 2),
+    "et_heatmap_targets": (ctypes.c_int, [ctypes.c_int32] * 4 + [_P] + [ctypes.c_double] * 2 + [_P, _P]),
+    "et_debug_host_heatmap_targets": (ctypes.c_int, [ctypes.c_int32] * 4 + [_P] + [ctypes.c_double] * 2 + [_P]),
+    "et_heatmap_loss": (ctypes.c_int, [ctypes.c_int32] * 5 + [_P] * 3 + [ctypes.c_double] * 2 + [_P, ctypes.c_int32] + [_P] * 4),
+    "et_debug_host_heatmap_loss": (ctypes.c_int, [ctypes.c_int32] * 5 + [_P] * 3 + [ctypes.c_double] * 2 + [_P, ctypes.c_int32] + [_P] * 3),
+    "et_heatmap_loss_bwd": (ctypes.c_int, [ctypes.c_int32] * 5 + [_P] * 3 + [ctypes.c_double] * 2 + [_P] * 5),
+    "et_debug_host_heatmap_loss_bwd": (ctypes.c_int, [ctypes.c_int32] * 5 + [_P] * 3 + [ctypes.c_double] * 2 + [_P] * 4),
     "et_nchw_to_nhwc": (ctypes.c_int, [ctypes.c_int32] * 4 + [_P, _P, _P]),
     "et_nhwc_to_nchw": (ctypes.c_int, [ctypes.c_int32] * 4 + [_P, _P, _P]),
     "et_debug_host_sample_setup": (ctypes.c_int, [_D, _P, _P, _P, _P, ctypes.c_int32, ctypes.c_int32, _P, _P, _P]),

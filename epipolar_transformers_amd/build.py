@@ -32,6 +32,7 @@ UNITS = {
     "et_triangulate.hip": ["et_triangulate.h", "et_wave_reduce.h"],
     "et_rpsm.hip": ["et_rpsm.h"],
     "et_metrics.hip": ["et_metrics.h", "et_wave_reduce.h"],
+    "et_loss.hip": ["et_loss.h"],
 }
 LIB = os.path.join(PKG, "lib", "libepipolar_amd.so")
 OBJ = os.path.join(PKG, "lib", "obj")

@@ -200,6 +200,8 @@ def default_cfg() -> CfgNode:
                                               # (ops.triangulate_views) instead of the batched torch DLT; rpsm without its dict is pymvg
     C.EPIPOLAR_AMD.EVAL_METRICS = False       # True: evaluation also computes the reference's test-time metrics on the device --
                                               # DATASETS.H36M.MAPPING, EPEmean_global, JDR and PCK@th (ops.eval_epe / eval_jdr / eval_pck)
+    C.EPIPOLAR_AMD.LOSS_KERNELS = False       # True: training takes its loss from the HIP kernels (ops.heatmap_loss) -- KEYPOINT.LOSS joint |
+                                              # smoothmse | mse is read, and without `heatmap` the target is made from `points-2d` on the fly
     C.EPIPOLAR_AMD.TRUNK_DTYPE = "fp32"       # arithmetic of the stock trunk (convolutions of `PoseResNet.trunk`): fp32 (the reference's)
                                               # | bf16 | fp16 = torch.autocast around it; the epipolar layer stays fp32 either way
     return C

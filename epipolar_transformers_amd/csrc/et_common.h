@@ -29,6 +29,8 @@
 //                                                    kernels, float32, no pairwise table; host + device routine
 //   et_metrics.hip        et_metrics.h               the test-time metrics of Modelbuilder.forward: JDR (block arg-max per map), PCK
 //                                                    counts, EPEmean in float64 with a fixed summation order; host + device routine
+//   et_loss.hip           et_loss.h                  the training loss: Heatmapcreator's targets, KEYPOINT.LOSS joint / smoothmse / mse and
+//                                                    their gradient, float64 sums in a fixed order; host + device routine
 //   et_misc.hip           kernels_misc.inc           sample_locs, residual epilogue, NCHW <-> NHWC, ABI version / errors
 //                         et_peaks.h                 the head's peak finder for one map (et_heatmap_peaks); host + device routine
 //   et_wave_reduce.h                                 DPP wave reductions (wave_all_sum / max / min): general, tile, GEMM units

@@ -77,6 +77,10 @@ class MultiViewPoseModel(nn.Module):
 
             convert_sync_batchnorm(self)
         self.criterion = JointsMSELoss(bool(getattr(cfg.KEYPOINT, "LOSS_PER_JOINT", False)))
+        from .config import amd_knob
+
+        if amd_knob(cfg, "LOSS_KERNELS", False):
+            self.loss_kind()                                               # an unknown KEYPOINT.LOSS fails here, not at the first step
 
     # ------------------------------------------------------------------------------------------ N1
     def forward_views(self, img: torch.Tensor, KRT: torch.Tensor, source_index: torch.Tensor,
@@ -259,6 +263,41 @@ class MultiViewPoseModel(nn.Module):
             for i, th in enumerate(thresholds):
                 metric_dict["PCK@" + str(th)] = pck[i]
 
+    # ------------------------------------------------------------------------------------------ training loss
+    def loss_kind(self) -> str:
+        """KEYPOINT.LOSS (model.py:59-71): joint when absent, smoothmse or mse; anything else is a ValueError."""
+        kind = getattr(self.cfg.KEYPOINT, "LOSS", "joint")
+        if kind not in ops.LOSS_KINDS:
+            raise ValueError("KEYPOINT.LOSS %r is none of %s" % (kind, ", ".join(ops.LOSS_KINDS)))
+        return kind
+
+    def kernel_losses(self, inputs: dict, heat, loss_dict: dict):
+        """The training loss of Modelbuilder.forward (model.py:249-258) through ops.heatmap_loss, into `loss_dict`: the criterion
+        KEYPOINT.LOSS names -- joint and smoothmse on heat[0] as `stage_loss0`, weighted by `visibility` (M,J) or (M,J,1); mse as
+        compute_stage_loss does, `stage_loss{i}` for every map of `heat`, visibility ignored (the reference's non-H36M call: its
+        H36M branch raises under mse).  The target is the batch's `heatmap`; without it `points-2d` (M,J,>=2), from which the
+        kernels make Heatmapcreator's target on the fly with KEYPOINT.SIGMA, BACKBONE.DOWNSAMPLE and the predicted map's own
+        size; without both there is no loss."""
+        kind = self.loss_kind()
+        target, points = inputs.get("heatmap"), inputs.get("points-2d")
+        if target is None and points is None:
+            return
+        dev = heat[0].device
+        how = {}
+        if target is not None:
+            target = target.to(dev, torch.float32).contiguous()
+        else:
+            how = dict(points=points[..., :2].to(dev, torch.float64).contiguous(), sigma=float(self.cfg.KEYPOINT.SIGMA),
+                       downsample=float(self.cfg.BACKBONE.DOWNSAMPLE))
+        vis = inputs.get("visibility")
+        if kind == "mse" or vis is None:
+            vis = None
+        else:
+            vis = vis.to(dev, torch.float32).reshape(heat[0].shape[:2]).contiguous()
+        per_joint = bool(getattr(self.cfg.KEYPOINT, "LOSS_PER_JOINT", False))
+        for i, maps in enumerate(heat if kind == "mse" else heat[:1]):
+            loss_dict["stage_loss%d" % i] = ops.heatmap_loss(maps.to(torch.float32), target, vis, kind=kind, per_joint=per_joint, **how)
+
     # ------------------------------------------------------------------------------------------ Modelbuilder.forward
     def forward(self, inputs: dict, is_train: bool = True):
         """The multiview_keypoint branch of Modelbuilder.forward (model.py:160-302).  `inputs` holds the reference's
@@ -284,7 +323,11 @@ class MultiViewPoseModel(nn.Module):
           * unless cfg.TEST.PCK is false (absent counts as true, the reference's default): `metrics_2d` -- "JDR" and
             out["jdr_per_joint"] given a target `heatmap`, "PCK@<th>", out["err_joints"] and out["total_joints"] given `points-2d`
             (M,J,>=2; the J joints that remain after the mapping).
-        The per-action and per-joint-name keys (MPJPE@<action>, JDR@<name>) need the data set's name tables and are not written."""
+        The per-action and per-joint-name keys (MPJPE@<action>, JDR@<name>) need the data set's name tables and are not written.
+
+        EPIPOLAR_AMD.LOSS_KERNELS (default off: training computes the torch JointsMSELoss above from `heatmap`) takes the training
+        loss from the HIP kernels instead (`kernel_losses`): KEYPOINT.LOSS joint | smoothmse | mse is read, and a batch without
+        `heatmap` but with `points-2d` gets its target made on the device, never stored."""
         cfg = self.cfg
         img = inputs["img"]
         KRT = inputs["KRT"].to(torch.float32)                               # model.py:183-185
@@ -326,7 +369,9 @@ class MultiViewPoseModel(nn.Module):
                 if heat is not None:
                     heat = [take(heat[0])] + list(heat[1:])
                 target_heat, batch_locs, batch_scos, visibility = take(target_heat), take(batch_locs), take(batch_scos), take(visibility)
-        if is_train and inputs.get("heatmap") is not None:
+        if is_train and amd_knob(cfg, "LOSS_KERNELS", False):
+            self.kernel_losses(inputs, heat, loss_dict)
+        elif is_train and inputs.get("heatmap") is not None:
             vis = inputs.get("visibility")
             vis = torch.ones(heat[0].shape[:2], device=heat[0].device) if vis is None else vis.to(torch.float32)
             loss_dict["stage_loss0"] = self.criterion(heat[0], inputs["heatmap"].to(torch.float32), vis)   # model.py:253

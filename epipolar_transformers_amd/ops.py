@@ -980,6 +980,100 @@ def eval_epe(pred: torch.Tensor, gt: torch.Tensor, vis: torch.Tensor = None, *, 
     return mean, per_joint
 
 
+LOSS_KINDS = {"joint": _lib.ET_LOSS_JOINT, "smoothmse": _lib.ET_LOSS_SMOOTHMSE, "mse": _lib.ET_LOSS_MSE}
+
+
+def _require_points(points: torch.Tensor, shape, device):
+    _require_gpu(points, "points", torch.float64)
+    if points.device != device or not points.is_contiguous() or tuple(points.shape) != tuple(shape):
+        raise ValueError("points must be a contiguous float64 tensor of shape %s on %s, got %s on %s" % (
+            tuple(shape), device, tuple(points.shape), points.device))
+
+
+def heatmap_targets(points: torch.Tensor, H: int, W: int, sigma: float, downsample: float) -> torch.Tensor:
+    """Heatmapcreator.get (data/transforms/keypoints2d.py:3-36) on the device (et_heatmap_targets): points (N,J,2) float64, (u, v) in
+    image pixels -> the (N,J,H,W) float32 targets the reference's data loader makes on the CPU, with its arithmetic: float32 grid,
+    float64 distance, exp rounded once to float32; v pairs with the rows; no visibility mask; the background is 0.01, not 0.
+    H * W <= 16384.  No synchronisation.  No gradient."""
+    _require_gpu(points, "points", torch.float64)
+    if points.dim() != 3 or points.shape[-1] != 2:
+        raise ValueError("points must be (N,J,2), got %s" % (tuple(points.shape),))
+    n, j, _ = points.shape
+    _require_points(points, (n, j, 2), points.device)
+    out = _empty((n, j, int(H), int(W)), device=points.device)
+    _call("et_heatmap_targets", points, n, j, int(H), int(W), _ptr(points), float(sigma), float(downsample), _ptr(out), _stream(points))
+    return out
+
+
+class HeatmapLoss(torch.autograd.Function):
+    """et_heatmap_loss / et_heatmap_loss_bwd.  Only `pred` receives a gradient; grad_output and the denominator stay on the
+    device."""
+
+    @staticmethod
+    def forward(ctx, pred, target, points, weight, kind, per_joint, sigma, downsample):
+        n, j, h, w = pred.shape
+        dev = pred.device
+        partials = _empty((n * j,), device=dev, dtype=torch.float64)
+        loss = _empty((), device=dev)
+        den = _empty((), device=dev, dtype=torch.float64)
+        _call("et_heatmap_loss", pred, kind, n, j, h, w, _ptr(pred), _ptr(target), _ptr(points), sigma, downsample, _ptr(weight),
+              int(per_joint), _ptr(partials), _ptr(loss), _ptr(den), _stream(pred))
+        ctx.save_for_backward(pred, target, points, weight, den)
+        ctx.call = (kind, sigma, downsample)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        pred, target, points, weight, den = ctx.saved_tensors
+        kind, sigma, downsample = ctx.call
+        n, j, h, w = pred.shape
+        go = grad_out.to(pred.device, torch.float32).reshape(1).contiguous()
+        grad = _empty(None, like=pred)
+        _call("et_heatmap_loss_bwd", pred, kind, n, j, h, w, _ptr(pred), _ptr(target), _ptr(points), sigma, downsample, _ptr(weight),
+              _ptr(den), _ptr(go), _ptr(grad), _stream(pred))
+        return grad, None, None, None, None, None, None, None
+
+
+def heatmap_loss(pred: torch.Tensor, target: torch.Tensor = None, weight: torch.Tensor = None, *, kind: str, per_joint: bool = False,
+                 points: torch.Tensor = None, sigma: float = None, downsample: float = None) -> torch.Tensor:
+    """The criterion KEYPOINT.LOSS names (modeling/model.py:59-71) of pred (N,J,H,W) float32 as a float32 scalar on the device, with
+    its gradient for `pred` (et_heatmap_loss / et_heatmap_loss_bwd: one pass over the maps each way, float64 sums in a fixed order,
+    no atomics, no synchronisation).  `kind`:
+      joint       JointsMSELoss (metrics2d.py:18-41): per joint the mean of (pred * w - gt * w) ** 2 over batch and pixels, summed over
+                  the joints and divided by J unless `per_joint`;
+      smoothmse   KeypointsMSESmoothLoss (:43-58): t = (gt - pred) ** 2 * w, replaced by t ** 0.1 * 400 ** 0.9 where t > 400, summed
+                  and divided by H * W * max(1, sum(w)); w carries no gradient;
+      mse         MaskedMSELoss with masks=None (:61-81): the mean of (pred - gt) ** 2; `weight` must be None.
+    The target is EITHER `target` (N,J,H,W) float32 OR `points` (N,J,2) float64 with `sigma` and `downsample`: then every lane makes
+    the target of its own pixels as heatmap_targets does and no dense target is read or written.  `weight`: (N,J) or (N,J,1) float32,
+    None = ones.  A `pred` that is not contiguous (the head of a channels-last trunk) is copied once; target, points and weight
+    must be contiguous.  H * W <= 16384."""
+    if kind not in LOSS_KINDS:
+        raise ValueError("kind must be one of %s, got %r" % (", ".join(LOSS_KINDS), kind))
+    if (target is None) == (points is None):
+        raise ValueError("give either target or points (with sigma and downsample), not %s" % ("neither" if target is None else "both"))
+    if kind == "mse" and weight is not None:
+        raise ValueError("kind 'mse' takes no weight (MaskedMSELoss with masks=None)")
+    _require_gpu(pred, "pred")
+    if pred.dim() != 4:
+        raise ValueError("pred must be (N,J,H,W), got %s" % (tuple(pred.shape),))
+    n, j, h, w = pred.shape
+    dev = pred.device
+    if target is not None:
+        _require_f32(target, "target", dev, (n, j, h, w))
+        sigma = downsample = 0.0
+    else:
+        if sigma is None or downsample is None:
+            raise ValueError("points need sigma and downsample")
+        _require_points(points, (n, j, 2), dev)
+    if weight is not None:
+        _require_gpu(weight, "weight")
+        if tuple(weight.shape) not in ((n, j), (n, j, 1)):
+            raise ValueError("weight must be (N,J) or (N,J,1) = (%d,%d[,1]), got %s" % (n, j, tuple(weight.shape)))
+        _require_f32(weight, "weight", dev)
+    return HeatmapLoss.apply(pred.contiguous(), target, points, weight, LOSS_KINDS[kind], bool(per_joint), float(sigma), float(downsample))
+
+
 def rpsm_workspace_bytes(frames: int, joints: int, first_nbins: int, recur_nbins: int) -> int:
     return int(_lib.load().et_rpsm_workspace_bytes(int(frames), int(joints), int(first_nbins), int(recur_nbins)))
 

@@ -567,6 +567,61 @@ int et_debug_host_eval_pck(int32_t N, int32_t J, const float *locs, const double
 int et_debug_host_eval_epe(int32_t F, int32_t J, const double *pred, const double *gt, const float *vis, double unit, double max_dist,
                            double *mean, double *per_joint);
 
+/* The training loss of Modelbuilder.forward (modeling/model.py:59-71, 249-258) and the heat-map targets of its data loader, on the
+ * device.  Maps hold at most 16384 elements (H, W >= 1, H * W <= 16384); N, J >= 1.  No call synchronises, none uses atomics:
+ * every output is bit-reproducible, and the host hooks below give the bits of the kernels wherever no exp or pow is involved
+ * (their exp and pow are the C library's, the kernels' the device library's: both well inside what one rounding to float32
+ * hides, except next to a rounding midpoint).
+ *
+ * et_heatmap_targets: Heatmapcreator.get (data/transforms/keypoints2d.py:3-36), called without valid_vec as the data set does.
+ *   points : (N, J, 2) float64, (u, v) in image pixels ;  out : (N, J, H, W) float32
+ * s = sigma * 2**0.5 in float64.  The grid value of row i is float32(float32(float32(i) * float32(downsample) +
+ * float32(downsample / 2.0 - 0.5)) / float32(s)) -- one IEEE float32 division -- and the same for column k.  r = v / s - grid_i:
+ * v, the SECOND coordinate, pairs with the row; c = u / s - grid_k; q = r * r + c * c, all float64; out = float32(exp(-min(q,
+ * 4.60517019))).  There is no visibility mask and the background is float32(exp(-4.60517019)) = 0.01, not zero. */
+int et_heatmap_targets(int32_t N, int32_t J, int32_t H, int32_t W, const double *points, double sigma, double downsample, float *out,
+                       void *stream);
+
+/* et_heatmap_loss: the criterion `kind` of predicted against target heat maps, a float32 scalar.
+ *   pred    : (N, J, H, W) float32
+ *   target  : (N, J, H, W) float32, or NULL with points : (N, J, 2) float64 and sigma / downsample -- then every lane makes the
+ *             target value of its own pixels as et_heatmap_targets does and no dense target exists.  Exactly one of the two.
+ *   weight  : (N, J) float32 or NULL (ones); must be NULL for ET_LOSS_MSE
+ *   partials: N * J float64 of scratch, the caller's (any contents before, unspecified after)
+ *   loss    : 1 float32 ;  den : 1 float64, the denominator -- et_heatmap_loss_bwd reads it
+ * The float32 term of an element, each operation rounded once, as the reference computes it:
+ *   ET_LOSS_JOINT      (JointsMSELoss)            d = pred * w - gt * w ;  term = d * d ;  den = N * H * W * (per_joint ? 1 : J)
+ *   ET_LOSS_SMOOTHMSE  (KeypointsMSESmoothLoss)   d = gt - pred ;  t = (d * d) * w ;  term = t, or float32(t ** 0.1) * float32(400 **
+ *                                                 0.9) where t > 400 ;  den = H * W * max(1, sum of the weights)
+ *   ET_LOSS_MSE        (MaskedMSELoss, no mask)   d = pred - gt ;  term = d * d ;  den = N * J * H * W
+ * loss = float32(sum / den), the sum in float64 in a fixed order: lane t of a map's 256 owns the 4-float quads
+ * first + t, first + t + 256, ... of the flat tensor (first = the quad the map starts in) and adds the elements of them that lie
+ * in the map in ascending order; the 256 partial sums go through a pairwise tree (p[t] += p[t + half], half = 128 .. 1); the
+ * per-map sums are added per joint over n ascending, then over the joints ascending.
+ * et_heatmap_loss_bwd: grad_pred (N, J, H, W) = d loss / d pred * grad_out[0]; grad_out and den are DEVICE pointers.  An
+ * element is float32(2 * d * w * c) for joint, float32(2 * d * c) for mse and float32(-2 * d * w * c), times 0.1 * t ** -0.9 *
+ * 400 ** 0.9 where t > 400, for smoothmse -- float64 from the float32 d, c = grad_out / den.  The weight carries no gradient. */
+#define ET_LOSS_JOINT 0
+#define ET_LOSS_SMOOTHMSE 1
+#define ET_LOSS_MSE 2
+int et_heatmap_loss(int32_t kind, int32_t N, int32_t J, int32_t H, int32_t W, const float *pred, const float *target,
+                    const double *points, double sigma, double downsample, const float *weight, int32_t per_joint, double *partials,
+                    float *loss, double *den, void *stream);
+int et_heatmap_loss_bwd(int32_t kind, int32_t N, int32_t J, int32_t H, int32_t W, const float *pred, const float *target,
+                        const double *points, double sigma, double downsample, const float *weight, const double *den,
+                        const float *grad_out, float *grad_pred, void *stream);
+
+/* Test hooks (HOST pointers, run on the CPU, no GPU needed): the per-lane routines of the three calls above (csrc/et_loss.h,
+ * shared with the kernels) in serial loops, in the kernels' summation order.  Not a CPU fallback of the path. */
+int et_debug_host_heatmap_targets(int32_t N, int32_t J, int32_t H, int32_t W, const double *points, double sigma, double downsample,
+                                  float *out);
+int et_debug_host_heatmap_loss(int32_t kind, int32_t N, int32_t J, int32_t H, int32_t W, const float *pred, const float *target,
+                               const double *points, double sigma, double downsample, const float *weight, int32_t per_joint,
+                               double *partials, float *loss, double *den);
+int et_debug_host_heatmap_loss_bwd(int32_t kind, int32_t N, int32_t J, int32_t H, int32_t W, const float *pred, const float *target,
+                                   const double *points, double sigma, double downsample, const float *weight, const double *den,
+                                   const float *grad_out, float *grad_pred);
+
 /* Layout converters between the reference's NCHW and the kernels' NHWC. */
 int et_nchw_to_nhwc(int32_t N, int32_t C, int32_t H, int32_t W, const float *src, float *dst, void *stream);
 int et_nhwc_to_nchw(int32_t N, int32_t C, int32_t H, int32_t W, const float *src, float *dst, void *stream);
