@@ -221,6 +221,33 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
+constexpr float kLargestFinite = 3.402823466e+38f;      // FLT_MAX: !(fabsf(v) <= kLargestFinite) <=> v is NaN or infinite
+
+// The order of every arg-max of the operator, torch.argmax's, as an unsigned key: a NaN ranks above every value (+Inf
+// included), then the larger value; -0 and +0 are one value.  Among equal keys the lowest index wins (the callers' part).
+// Every key of a value is > 0, so 0 serves as "no candidate yet".
+__device__ __forceinline__ unsigned argmax_key(float v)
+{
+    const unsigned u = __float_as_uint(v == 0.f ? 0.f : v);      // (-0 and +0: one key, whatever the floating-point flags)
+    return (v != v) ? 0xffffffffu : (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// Wave-wide: the index of the first maximum among the lanes' candidates (key from argmax_key, 0 = none; idx its sample).  With no
+// candidate in any lane the answer is sample 0 -- never an index outside the samples: callers use it as a lane id and an address.
+__device__ __forceinline__ int wave_first_argmax(unsigned key, int idx)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const unsigned ok = (unsigned)__shfl_xor((int)key, m);
+        const int oi = __shfl_xor(idx, m);
+        if (ok > key || (ok == key && oi < idx)) {
+            key = ok;
+            idx = oi;
+        }
+    }
+    return key ? idx : 0;
+}
+
 // max over the four rows of reduce4 (values already uniform inside a row)
 __device__ __forceinline__ float group_max(float v)
 {

@@ -121,17 +121,9 @@ __device__ __forceinline__ void gen_taps(const int4 *s_tap, const float4 *s_w, i
     }
 }
 
-// one channel of the pooled sample: the maximum of the two samples (epipolar.py:200-202, 211-213)
-template <bool POOL>
-__device__ __forceinline__ float gen_pooled(const float *map, int ch, int c, const int4 t0, const float4 w0, const int4 t1,
-                                            const float4 w1)
-{
-    float v = gen_sample(map, ch, c, t0, w0);
-    if (POOL) v = fmaxf(v, gen_sample(map, ch, c, t1, w1));
-    return v;
-}
-
-// ... and which sample won it: the second only when strictly larger (the first on a tie, as torch.max)
+// one channel of the pooled sample: the maximum of the two samples (epipolar.py:200-202, 211-213), and which sample won it --
+// torch.max's rule: a NaN is above every value (fmaxf would return the other operand and lose it), else the second only when
+// strictly larger (the first on a tie, and of two NaNs)
 template <bool POOL>
 __device__ __forceinline__ float gen_pooled_argwin(const float *map, int ch, int c, const int4 t0, const float4 w0,
                                                    const int4 t1, const float4 w1, bool &second)
@@ -141,10 +133,19 @@ __device__ __forceinline__ float gen_pooled_argwin(const float *map, int ch, int
     float v = v0;
     if (POOL) {
         const float v1 = gen_sample(map, ch, c, t1, w1);
-        second = v1 > v0;
+        second = (v1 > v0) | ((v1 != v1) & (v0 == v0));
         v = second ? v1 : v0;
     }
     return v;
+}
+
+// the value alone
+template <bool POOL>
+__device__ __forceinline__ float gen_pooled(const float *map, int ch, int c, const int4 t0, const float4 w0, const int4 t1,
+                                            const float4 w1)
+{
+    bool second;
+    return gen_pooled_argwin<POOL>(map, ch, c, t0, w0, t1, w1, second);
 }
 
 // lanes <-> channels: dot = q . P_k' over the wave, and vv = |P_k'|^2 (summed over the wave under the cosine similarity only)
@@ -172,20 +173,22 @@ __device__ __forceinline__ void gen_similarity(const GeneralParams &p, const flo
 constexpr int kGenKPL = 4;
 static_assert(kGenKPL * kWave == 256, "the lanes <-> samples phases must hold validate()'s largest K");
 
-// first maximum over k' (torch.argmax) of a[s] = value of k' = s * 64 + lane: largest value, then lowest index
+// first maximum over k' (torch.argmax) of a[s] = value of k' = s * 64 + lane: a NaN above every value, then the largest value,
+// then the lowest index (argmax_key); always one of 0 .. K'-1
 __device__ __forceinline__ int gen_first_argmax(const float (&a)[kGenKPL], int Ks, int lane)
 {
-    float bestv = -__builtin_huge_valf(), bestk = 1e9f;
+    unsigned bestk = 0u;
+    int besti = 0x7fffffff;
 #pragma unroll
     for (int s = 0; s < kGenKPL; ++s) {
         const int k = s * kWave + lane;
-        if (k < Ks && a[s] > bestv) {
-            bestv = a[s];
-            bestk = (float)k;
+        const unsigned key = argmax_key(a[s]);
+        if (k < Ks && key > bestk) {
+            bestk = key;
+            besti = k;
         }
     }
-    const float bm = wave_all_max(bestv);
-    return (int)wave_all_min((bestv == bm) ? bestk : 1e9f);
+    return wave_first_argmax(bestk, besti);
 }
 
 template <bool POOL>
@@ -245,7 +248,7 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_fwd_general_kernel(
                 v = d.softmax_enabled ? v * d.softmax_scale : v / (float)Ks;      // :306 / :311
             }
             l[s] = v;
-            if (in) vmax = fmaxf(vmax, v);
+            if (in) vmax = fmaxf(vmax, v);      // (the soft-max's maximum: a NaN it drops comes back as expf(NaN - vmax))
         }
         if (d.softmax_enabled && !p.attn_max && !p.sim_prior) {
             vmax = wave_all_max(vmax);
@@ -553,7 +556,9 @@ __global__ __launch_bounds__(kWave *kGenWaves) void epipolar_bwd_general_kernel(
         float *gqrow = bp.gq + ((size_t)n * HW + pix) * p.cs;
 #pragma unroll
         for (int i = 0; i < kGenMaxQ; ++i)
-            if (lane + i * kWave < p.cs) gqrow[lane + i * kWave] = dq[i] - gamma * qv[i];
+            // (gamma == 0 -- every similarity but the cosine, and ATTENTION max without a gradient through the attention --: q does
+            //  not enter its own gradient, and 0 x q must not either: a NaN or an Inf in q stays out, as in the reference's graph)
+            if (lane + i * kWave < p.cs) gqrow[lane + i * kWave] = gamma != 0.f ? dq[i] - gamma * qv[i] : dq[i];
     }
 }
 

@@ -30,14 +30,15 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_kernel(con
     const __amdgpu_buffer_rsrc_t gsrc = make_rsrc(p.gsrc + (size_t)n * HW * C, (unsigned)HW * C * 4u);
     const int row_bytes = C * 4;
     const float neg_inf = -__builtin_huge_valf();
-    // lanes beyond C (only when C < 64*CPD) alias the last channel: they read
-    // it again, contribute zero to every dot product and add 0.0f in flushes.
+    // lanes beyond C (only when C < 64*CPD) point past the buffer: their loads return zeros and their atomics are dropped
+    // (the range check of a raw buffer looks at the vector offset alone), so they contribute zero to every dot product.
+    // (They used to alias the last channel and add 0.0f to it: 0 x Inf = NaN, once a weight was infinite.)
     int voff[CPD];
     bool live[CPD];
 #pragma unroll
     for (int c = 0; c < CPD; ++c) {
         live[c] = (lane + c * kWave) < C;
-        voff[c] = min(lane + c * kWave, C - 1) * 4;
+        voff[c] = live[c] ? (lane + c * kWave) * 4 : 0x7ffff000;
     }
 
     for (int pp = 0; pp < kPixPerWave; ++pp) {
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_kernel(con
                             if (need & (1 << r)) {
                                 const int off = __builtin_amdgcn_readlane(tb.off[s][r], kk);
 #pragma unroll
-                                for (int c = 0; c < CPD; ++c) R[r][c] = buf_load_f1(src, voff[c], off);
+                                for (int c = 0; c < CPD; ++c) R[r][c] = tap_row_f1(src, voff[c], off);
                             }
                         }
                         const float w0 = lane_bcast(tb.w[s][0], kk), w1 = lane_bcast(tb.w[s][1], kk);
@@ -133,15 +134,14 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_kernel(con
                 for (int r = 0; r < 4; ++r) {
                     if (need & (1 << r)) {
                         const int off = __builtin_amdgcn_readlane(tb.off[s][r], kk);
-                        if (tag[r] >= 0) {
+                        // (what an absent tap gathered -- weight 0 times dS, NaN once dS is infinite -- belongs to no row: dropped)
 #pragma unroll
-                            for (int c = 0; c < CPD; ++c) {
-                                __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(G[r][c], gsrc, voff[c], tag[r], 0);
-                                G[r][c] = 0.f;
-                            }
+                        for (int c = 0; c < CPD; ++c) {
+                            if (tag[r] >= 0) __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(G[r][c], gsrc, voff[c], tag[r], 0);
+                            G[r][c] = 0.f;
                         }
 #pragma unroll
-                        for (int c = 0; c < CPD; ++c) R[r][c] = buf_load_f1(src, voff[c], off);
+                        for (int c = 0; c < CPD; ++c) R[r][c] = tap_row_f1(src, voff[c], off);
                         tag[r] = off;
                     }
                 }
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_emit_kerne
     const float neg_inf = -__builtin_huge_valf();
     int voff[CPL];
 #pragma unroll
-    for (int c = 0; c < CPL; ++c) voff[c] = min(lane + c * kWave, nvec - 1) * 16;
+    for (int c = 0; c < CPL; ++c) voff[c] = (lane + c * kWave < nvec) ? (lane + c * kWave) * 16 : 0x7ffff000;   // (idle lanes: zeros, as in the forward)
 
     for (int pp = 0; pp < kPixPerWave; ++pp) {
         const int pix = pix_base + pp * kWavesPerBlock + wave;  // waves of a block on neighbouring pixels
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_emit_kerne
                             if (need & (1 << r)) {
                                 const int off = __builtin_amdgcn_readlane(tb.off[s][r], kk);
 #pragma unroll
-                                for (int c = 0; c < CPL; ++c) R[r][c] = buf_load_f4(src, voff[c], off);
+                                for (int c = 0; c < CPL; ++c) R[r][c] = tap_row_f4(src, voff[c], off);
                             }
                         }
                         const float4 wv = s_wt[s * kWave + kk];
@@ -297,10 +297,25 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_emit_kerne
         }
         int tag[4] = {-1, -1, -1, -1};
         float ea[4] = {0.f, 0.f, 0.f, 0.f}, eb[4] = {0.f, 0.f, 0.f, 0.f};
+        // A pixel whose grad_out / feat_ref row holds an Inf: the gather pass multiplies the SUMS alpha_u, beta_u with that row,
+        // the reference multiplies term by term -- w a_k g with terms of both signs (or a zero one) is Inf - Inf (0 x Inf) = NaN
+        // there, alpha_u x Inf = +-Inf here.  So such a pixel (wave-uniform, rare) also records, per entry, whether its terms are
+        // of one strict sign (bit 0: positive, 1: negative, 2: zero or NaN seen), and the entry carries "mixed" flags in the
+        // upper bits of its row index (bit 24: alpha, bit 25: beta) for the gather pass, which turns Inf factors into NaN then.
+        bool odd_row = false;
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+            auto odd = [](float x) { return !(fabsf(x) <= kLargestFinite); };
+            odd_row |= odd(f1[c].x) | odd(f1[c].y) | odd(f1[c].z) | odd(f1[c].w) | odd(g[c].x) | odd(g[c].y) | odd(g[c].z) | odd(g[c].w);
+        }
+        const bool odd_pixel = __builtin_amdgcn_ballot_w64(odd_row) != 0;
+        int fa[4] = {0, 0, 0, 0}, fb[4] = {0, 0, 0, 0};
+        auto sign_bits = [](float t) { return t > 0.f ? 1 : t < 0.f ? 2 : 4; };
+        auto mixed = [](int f) { return (f & 4) != 0 || (f & 3) == 3; };
         int ecount = 0;
         auto emit = [&](int r) {  // wave-uniform call
             if (lane == 0) {
-                s_eu[ecount] = tag[r] / row_bytes;
+                s_eu[ecount] = (tag[r] / row_bytes) | (mixed(fa[r]) ? 1 << 24 : 0) | (mixed(fb[r]) ? 1 << 25 : 0);
                 s_ea[ecount] = ea[r];
                 s_eb[ecount] = eb[r];
             }
@@ -318,8 +333,12 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_emit_kerne
                     if (need & (1 << r)) {
                         const int off = __builtin_amdgcn_readlane(tb.off[s][r], kk);
                         if (tag[r] >= 0) emit(r);
+                        ea[r] = 0.f;      // (what an absent tap gathered, weight 0 times a_k / ds_k, belongs to no row: dropped)
+                        eb[r] = 0.f;
+                        fa[r] = 0;
+                        fb[r] = 0;
 #pragma unroll
-                        for (int c = 0; c < CPL; ++c) R[r][c] = buf_load_f4(src, voff[c], off);
+                        for (int c = 0; c < CPL; ++c) R[r][c] = tap_row_f4(src, voff[c], off);
                         tag[r] = off;
                     }
                 }
@@ -332,6 +351,14 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_emit_kerne
                 ea[1] = fmaf(wv.y, ak_src, ea[1]); eb[1] = fmaf(wv.y, dsk_src, eb[1]);
                 ea[2] = fmaf(wv.z, ak_src, ea[2]); eb[2] = fmaf(wv.z, dsk_src, eb[2]);
                 ea[3] = fmaf(wv.w, ak_src, ea[3]); eb[3] = fmaf(wv.w, dsk_src, eb[3]);
+                if (odd_pixel) {  // wave-uniform
+                    const float w4[4] = {wv.x, wv.y, wv.z, wv.w};
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        fa[r] |= sign_bits(w4[r] * ak_src);
+                        fb[r] |= sign_bits(w4[r] * dsk_src);
+                    }
+                }
 #pragma unroll
                 for (int c = 0; c < CPL; ++c) {
                     float4 sv = f4_mul(wv.x, R[0][c]);
@@ -348,8 +375,8 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_bwd_emit_kerne
         __builtin_amdgcn_wave_barrier();
         const size_t ebase = ((size_t)n * HW + pix) * p.cap;
         for (int i = lane; i < ecount; i += kWave) {
-            const int u = s_eu[i];
-            p.ent_u[ebase + i] = u;
+            const int u = s_eu[i] & 0xffffff;      // (the flags travel in ent_u)
+            p.ent_u[ebase + i] = s_eu[i];
             p.ent_a[ebase + i] = s_ea[i];
             p.ent_b[ebase + i] = s_eb[i];
             atomicAdd(&p.row_count[(size_t)n * HW + u], 1);
@@ -414,13 +441,14 @@ __global__ __launch_bounds__(256) void bwd_bucket_kernel(int HW, int cap, int to
         const size_t ebase = (size_t)gp * cap;
         const size_t pair_rows = (size_t)n * HW;
         for (int slot = lane; slot < cnt; slot += kWave) {
-            const int u = ent_u[ebase + slot];
+            const int eu = ent_u[ebase + slot];
+            const int u = eu & 0xffffff;
             const size_t gu = pair_rows + u;
             const int pos = row_base[gu] + atomicAdd(&row_cursor[gu], 1);
             const size_t o = pair_rows * cap + pos;     // per-pair CSR region of HW*cap slots
-            // one 16-byte record per entry (a single scattered store): {ordering key, alpha, beta, -}
+            // one 16-byte record per entry (a single scattered store): {ordering key, alpha, beta, mixed-sign flags}
             csr[o] = make_int4(pidx * cap + slot, __float_as_int(ent_a[ebase + slot]),
-                               __float_as_int(ent_b[ebase + slot]), 0);
+                               __float_as_int(ent_b[ebase + slot]), eu >> 24);
         }
     }
 }
@@ -477,21 +505,35 @@ __global__ __launch_bounds__(256) void epipolar_bwd_gather_kernel(int HW, int C,
     auto accumulate = [&](int count, auto index_of) {
         for (int e0 = 0; e0 < count; e0 += kWave) {
             const int m = min(kWave, count - e0);
-            int pp = 0;
+            int pp = 0, ff = 0;
             float aa = 0.f, bb = 0.f;
             if (lane < m) {
                 const int4 rec = csr[seg + index_of(e0 + lane)];
                 pp = rec.x / cap;
                 aa = __int_as_float(rec.y);
                 bb = __int_as_float(rec.z);
+                ff = rec.w;
             }
             for (int j = 0; j < m; ++j) {
                 const int pj = __builtin_amdgcn_readlane(pp, j) * row_bytes;  // scalar row offset
                 const float aj = lane_bcast(aa, j), bj = lane_bcast(bb, j);
+                const int fj = __builtin_amdgcn_readlane(ff, j);              // (0 unless the pixel's row holds an Inf: emit kernel)
 #pragma unroll
                 for (int c = 0; c < CPL; ++c) {
                     if (mask & 2) acc[c] = f4_fma(aj, buf_load_f4(G4, voff[c] * 16, pj), acc[c]);
                     if (mask & 1) acc[c] = f4_fma(bj, buf_load_f4(F4, voff[c] * 16, pj), acc[c]);
+                }
+                if (fj != 0) {  // wave-uniform: terms of mixed sign times an infinite factor are NaN in the reference
+                    auto nan_of_inf = [](float4 v) {
+                        auto h = [](float x) { return fabsf(x) == __builtin_huge_valf() ? __builtin_nanf("") : 0.f; };
+                        return make_float4(h(v.x), h(v.y), h(v.z), h(v.w));
+                    };
+                    auto f4_add = [](const float4 &a, const float4 &b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); };
+#pragma unroll
+                    for (int c = 0; c < CPL; ++c) {
+                        if ((mask & 2) && (fj & 1)) acc[c] = f4_add(acc[c], nan_of_inf(buf_load_f4(G4, voff[c] * 16, pj)));
+                        if ((mask & 1) && (fj & 2)) acc[c] = f4_add(acc[c], nan_of_inf(buf_load_f4(F4, voff[c] * 16, pj)));
+                    }
                 }
             }
         }

@@ -27,8 +27,9 @@
 // every partial sum stays below 2^62 and every contribution below 2^48 quanta, and a contribution AT the bound keeps 47 bits.
 // q is clamped to >= 2^-100 so that 1 / q and acc * q are exact normal fp32 arithmetic.  With the soft-max off the
 // "attention" is sim / K (-1e10 / K under the mask): no useful bound -- the entry point refuses that case.
-// A contribution of 2^48 quanta or more (or a NaN) cannot happen under the bound; the tile kernel checks it all the same, ORs
-// kDetGuardMask (bit 2) into the workspace's sticky error word and does not add it.
+// A finite contribution of 2^48 quanta or more cannot happen under the bound; the tile kernel checks it all the same, ORs
+// kDetGuardMask (bit 2) into the workspace's sticky error word and does not add it.  A contribution that is NaN or infinite -- the
+// pair holds a non-finite input; the maxima above skip such values -- marks its element instead, and the element comes out NaN.
 
 // (kDetMaxBlocks, the blocks per pair of det_maxima_kernel -- one partial result each: et_tile_layout.h)
 constexpr int kDetQuantumMinExp = -100;     // (an fp32 bound gives at most 2^81: no upper clamp is needed)
@@ -61,7 +62,7 @@ __host__ __device__ inline DetQuantum det_quantum(float softmax_scale, float m_r
 
 // max |.| of the three maps of every pair (and of its rows of gattn = d loss / d attn, nullable: K H W floats per pair): block
 // (b, n) takes every gridDim.x-th run of 256 float4 of pair n and leaves { M_ref, M_src, M_g, M_ga } in
-// partial[(n * gridDim.x + b) * 4 ..] (fmaxf: a NaN is skipped -- it trips the guard later)
+// partial[(n * gridDim.x + b) * 4 ..] (finite values only)
 __global__ __launch_bounds__(256) void det_maxima_kernel(const float4 *__restrict__ fref, const float4 *__restrict__ fsrc,
                                                          const float4 *__restrict__ gout, unsigned vec4_per_pair,
                                                          const float *__restrict__ gattn, unsigned ga_per_pair,
@@ -70,11 +71,14 @@ __global__ __launch_bounds__(256) void det_maxima_kernel(const float4 *__restric
     __shared__ float s_m[4][4];
     const int n = blockIdx.y;
     const size_t base = (size_t)n * vec4_per_pair;
-    auto amax4 = [](float m, const float4 &v) { return fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w))); };
+    // (a NaN or an Inf counts as 0: the quantum is made for the pair's FINITE values, which then keep their accuracy; what a
+    //  non-finite value contributes is non-finite and is marked, not scaled: det_add)
+    auto mag = [](float x) { const float a = fabsf(x); return a <= kLargestFinite ? a : 0.f; };
+    auto amax4 = [&](float m, const float4 &v) { return fmaxf(fmaxf(m, fmaxf(mag(v.x), mag(v.y))), fmaxf(mag(v.z), mag(v.w))); };
     float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f;
     if (gattn) {    // (scalar loads: K H W need not be a multiple of four)
         const float *ga = gattn + (size_t)n * ga_per_pair;
-        for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < ga_per_pair; i += gridDim.x * blockDim.x) m3 = fmaxf(m3, fabsf(ga[i]));
+        for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < ga_per_pair; i += gridDim.x * blockDim.x) m3 = fmaxf(m3, mag(ga[i]));
     }
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < vec4_per_pair; i += gridDim.x * blockDim.x) {
         const float4 a = fref[base + i], b = fsrc[base + i], c = gout[base + i];
@@ -125,6 +129,8 @@ __global__ __launch_bounds__(256) void det_finish_kernel(const long long *__rest
     const float q = quanta[blockIdx.y * 4];
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < vec4_per_pair; i += gridDim.x * blockDim.x) {
         const i64x2 lo = __builtin_nontemporal_load(a + 2 * i), hi = __builtin_nontemporal_load(a + 2 * i + 1);
-        gsrc[i] = make_float4((float)lo.x * q, (float)lo.y * q, (float)hi.x * q, (float)hi.y * q);
+        // (an element beyond 2^61 was marked non-finite by det_add: NaN)
+        auto val = [q](long long a) { return (a < kDetPoisonFloor && a > -kDetPoisonFloor) ? (float)a * q : __builtin_nanf(""); };
+        gsrc[i] = make_float4(val(lo.x), val(lo.y), val(hi.x), val(hi.y));
     }
 }

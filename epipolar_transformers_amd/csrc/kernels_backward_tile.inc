@@ -64,6 +64,7 @@ struct BwdTileParams {
                             // kDetHardParts blocks there)
 };
 
+constexpr long long kDetPoison = 1LL << 62, kDetPoisonFloor = 1LL << 61;   // an accumulator element marked non-finite (det_add)
 constexpr int kDetGuardMask = 1 << 2;   // sticky error word, bit 2: a fixed-point contribution of the deterministic backward was out of range
 constexpr int kDetHardParts = 8;    // blocks of the second launch that share a deferred tile beyond that launch's own capacity
 
@@ -149,7 +150,7 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
     const __amdgpu_buffer_rsrc_t gout = make_rsrc(p.gout + (size_t)n * HW * C, map_bytes);
     const __amdgpu_buffer_rsrc_t gsrc = make_rsrc(p.gsrc + (size_t)n * HW * C, map_bytes);
     const float neg_inf = -__builtin_huge_valf();
-    // DET: the pair's int64 accumulator and 1 / q; a contribution of 2^48 quanta or more (or a NaN) -- impossible under the
+    // DET: the pair's int64 accumulator and 1 / q; a FINITE contribution of 2^48 quanta or more -- impossible under the
     // bound q is made from (kernels_backward_det.inc) -- is reported in the sticky error word and not added
     long long *det_pair = nullptr;
     float det_invq = 0.f;
@@ -157,10 +158,22 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
         det_pair = tp.det_acc + (size_t)n * HW * C;
         det_invq = tp.det_q[n * 4 + 1];
     }
+    // A contribution that is itself NaN or infinite (a non-finite input of this pair) is no error: the element is MARKED, set to
+    // kDetPoison once (compare-and-swap; later additions, each below 2^48 quanta and fewer than 2^14, leave it beyond 2^61, and a
+    // marked element is not marked again), and det_finish_kernel writes NaN for it -- whatever the order of arrival, so the call
+    // stays bit-reproducible, and never lost.
     auto det_add = [&](float v, long long *dst) {
         const float s = v * det_invq;
-        if (fabsf(s) < 0x1p48f) __hip_atomic_fetch_add(dst, __float2ll_rn(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else atomicOr(tp.det_err, kDetGuardMask);
+        if (fabsf(s) < 0x1p48f) {
+            __hip_atomic_fetch_add(dst, __float2ll_rn(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else if (!(fabsf(v) <= kLargestFinite)) {
+            long long cur = __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            while (cur < kDetPoisonFloor && cur > -kDetPoisonFloor &&
+                   !__hip_atomic_compare_exchange_strong(dst, &cur, kDetPoison, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+            }
+        } else {
+            atomicOr(tp.det_err, kDetGuardMask);
+        }
     };
 
     // ---- geometry, once per tile (as the forward) ----
@@ -296,7 +309,7 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
         }
         const int nb = (U + 31) >> 5;
         const int ucols = nb * 32;  // columns the GEMMs below read: pad the row list, keep those columns defined
-        if (tid < ucols - U) s_rows[U + tid] = 0;
+        if (tid < ucols - U) s_rows[U + tid] = kTilePadRow;      // (a row past the map: its loads return zeros)
         __syncthreads();
 
         // ---- D-type GEMM (the forward's phase 1, tile_gemm_rows): array = A_t . F2_U^T, A_t = the tile's rows of `abuf` ----

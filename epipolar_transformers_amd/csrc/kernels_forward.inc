@@ -32,12 +32,14 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, 5) void epipolar_fwd_kernel(
     const __amdgpu_buffer_rsrc_t src = make_rsrc(p.fsrc + (size_t)n * HW * C, (unsigned)HW * C * 4u);
     const int row_bytes = C * 4;
     const float neg_inf = -__builtin_huge_valf();
-    // Lanes beyond C/4 (only when C < 256*CPL) re-read the last channel group:
-    // their reference features are zeroed and their results never stored, so
-    // the hot loop carries no per-lane predicate and stays on scalar branches.
+    // Lanes beyond C/4 (only when C < 256*CPL) point past the buffer: their loads return zeros (the range check of a raw
+    // buffer looks at the vector offset alone, whatever row the scalar offset selects), their reference features are
+    // zeroed and their results never stored, so the hot loop carries no per-lane predicate and stays on scalar branches.
+    // (They used to re-read the last channel group: 0 x Inf = NaN then turned an infinite logit into a NaN.)
+    constexpr int kOob = 0x7ffff000;
     int voff[CPL];
 #pragma unroll
-    for (int c = 0; c < CPL; ++c) voff[c] = min(lane + c * kWave, nvec - 1) * 16;
+    for (int c = 0; c < CPL; ++c) voff[c] = (lane + c * kWave < nvec) ? (lane + c * kWave) * 16 : kOob;
 
     for (int pp = 0; pp < kPixPerWave; ++pp) {
         // pixels interleaved across the block's waves (wave w takes pixels w, w+4, ..), which keeps the
@@ -98,7 +100,7 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, 5) void epipolar_fwd_kernel(
                             if (need & (1 << r)) {
                                 const int off = __builtin_amdgcn_readlane(tb.off[s][r], kk);
 #pragma unroll
-                                for (int c = 0; c < CPL; ++c) R[r][c] = buf_load_f4(src, voff[c], off);
+                                for (int c = 0; c < CPL; ++c) R[r][c] = tap_row_f4(src, voff[c], off);
                             }
                         }
                         const float4 wv = s_wt[s * kWave + kk];
@@ -122,6 +124,8 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, 5) void epipolar_fwd_kernel(
                 if (d.softmax_enabled) {
                     sv = sv * d.softmax_scale;  // epipolar.py:306
                     const float bm = group_max(jvalid ? sv : neg_inf);
+                    // (fmaxf drops a NaN logit from the running maximum; it is not lost: exp(NaN - m) below is NaN, and so
+                    //  are the sum and every weight, as in torch's soft-max)
                     const float m_new = fmaxf(m_run, bm);
                     // accumulator weights only need ~1e-6 relative accuracy (the returned attention is
                     // recomputed with expf in the final pass): hardware exp2
@@ -271,9 +275,11 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock) void epipolar_fwd_multi_kern
 #pragma unroll
             for (int s = 0; s < KPL; ++s) {
                 const int k = s * kWave + lane;
-                // an absent tap (-1) is never loaded (its need bit is clear), so its offset can be anything
-                s_off[gg * KP + k] = make_int4((tb.off[s][0] & ~15) | (live ? tb.need[s] : 0), tb.off[s][1],
-                                               tb.off[s][2], tb.off[s][3]);
+                // an absent tap (-1) points past the buffer: when the step needs it (the register held a row before) the
+                // load returns zeros, so a stale row never meets its weight 0 (0 x NaN)
+                constexpr int kAbsent = 0x7ffff000;
+                auto offv = [&](int r) { return tb.off[s][r] < 0 ? kAbsent : tb.off[s][r]; };
+                s_off[gg * KP + k] = make_int4((offv(0) & ~15) | (live ? tb.need[s] : 0), offv(1), offv(2), offv(3));
                 s_wt[gg * KP + k] = make_float4(tb.w[s][0], tb.w[s][1], tb.w[s][2], tb.w[s][3]);
             }
         }

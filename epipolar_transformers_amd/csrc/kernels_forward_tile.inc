@@ -219,13 +219,14 @@ __device__ __forceinline__ void fwd_tile_body(const TileParams &tp, const int vb
                 m &= m - 1;
             }
         }
-        // phase 3 walks the rows in groups of 16: pad the list with row 0 of the source map (a valid address;
-        // the matching B columns are zero)
+        // phase 3 walks the rows in groups of 16: pad the list with a row past the map (loads return zeros; the matching
+        // B columns are zero too)
         const int upad = (U + 15) & ~15;
-        if (tid < upad - U) s_rows[U + tid] = 0;
+        if (tid < upad - U) s_rows[U + tid] = kTilePadRow;
         __syncthreads();
 
         bool split_ok = false;           // block-uniform: this (sub)tile's GEMMs run as split-fp16 products
+        bool odd_logit = false;          // per lane: a logit of this group is NaN or infinite (see behind phase 2)
         // ================= phase 1: D = F1_tile . F2_U^T on the matrix cores =================
         // fragment layout of v_mfma_f32_32x32x2_f32: lane l supplies A[m = l & 31][k = l >> 5] and
         // B[k = l >> 5][n = l & 31].  The k order is ours to choose as long as A and B agree: MFMA
@@ -313,6 +314,7 @@ __device__ __forceinline__ void fwd_tile_body(const TileParams &tp, const int vb
                         if (d.softmax_enabled) l = l * d.softmax_scale;  // epipolar.py:306
                         else l = l / (float)K;                           // epipolar.py:311
                         lg[j] = l;
+                        odd_logit |= !(fabsf(l) <= kLargestFinite);      // (lanes without a sample: -1e10 x scale, finite)
                     }
                     {
                         static_assert(PB == 4, "the wave reductions below are four wide");
@@ -339,12 +341,17 @@ __device__ __forceinline__ void fwd_tile_body(const TileParams &tp, const int vb
                             }
                             wave_all_max4(amax);
                         }
-                        // first maximum over k (torch.argmax)
+                        // first maximum over k (torch.argmax): a NaN is above every value -- the first NaN where there is one (v_max
+                        // dropped it from amax; behind the soft-max one NaN makes every weight NaN: sample 0) --, else the lowest
+                        // lane that holds the maximum.  No hit at all cannot address anything: masked to a lane where it is used.
 #pragma unroll
                         for (int j = 0; j < PB; ++j) idx[j] = (in && a[j] == amax[j]) ? (float)lane : 1e9f;
                         wave_all_min4(idx);
 #pragma unroll
-                        for (int j = 0; j < PB; ++j) best[j] = (int)idx[j];
+                        for (int j = 0; j < PB; ++j) {
+                            const unsigned long long nans = __builtin_amdgcn_ballot_w64(in && a[j] != a[j]);
+                            best[j] = nans ? (int)__builtin_ctzll(nans) : (int)idx[j];
+                        }
                     }
 #pragma unroll
                     for (int j = 0; j < PB; ++j) {
@@ -400,7 +407,8 @@ __device__ __forceinline__ void fwd_tile_body(const TileParams &tp, const int vb
                         if (d.softmax_enabled) l = l * d.softmax_scale;  // epipolar.py:306
                         else l = l / (float)K;                           // epipolar.py:311
                         sv[s] = l;
-                        if (in) vmax = fmaxf(vmax, l);
+                        odd_logit |= !(fabsf(l) <= kLargestFinite);
+                        if (in) vmax = fmaxf(vmax, l);      // (a NaN it drops comes back as expf(NaN - vmax) below)
                     }
                     float a[KPL];
                     if (d.softmax_enabled) {
@@ -418,18 +426,20 @@ __device__ __forceinline__ void fwd_tile_body(const TileParams &tp, const int vb
 #pragma unroll
                         for (int s = 0; s < KPL; ++s) a[s] = (s * kWave + lane < K) ? sv[s] : 0.f;
                     }
-                    // first maximum over k (torch.argmax): largest value, then lowest index
-                    float bestv = neg_inf, bestk = 1e9f;
+                    // first maximum over k (torch.argmax): a NaN above every value, then the largest value, then the lowest
+                    // index (argmax_key); always one of the samples
+                    unsigned bestk = 0u;
+                    int bestl = 0x7fffffff;
 #pragma unroll
                     for (int s = 0; s < KPL; ++s) {
                         const int k = s * kWave + lane;
-                        if (k < K && a[s] > bestv) {
-                            bestv = a[s];
-                            bestk = (float)k;
+                        const unsigned key = argmax_key(a[s]);
+                        if (k < K && key > bestk) {
+                            bestk = key;
+                            bestl = k;
                         }
                     }
-                    const float bm = wave_all_max(bestv);
-                    const int besti = (int)wave_all_min((bestv == bm) ? bestk : 1e9f);
+                    const int besti = wave_first_argmax(bestk, bestl);
                     if (p.corr) {
                         float bx = 0.f, by = 0.f;
 #pragma unroll
@@ -492,7 +502,14 @@ __device__ __forceinline__ void fwd_tile_body(const TileParams &tp, const int vb
             for (int ii = 0; ii < PW; ii += 2)
                 tile_convert_b_rows(s_D + (wave * PW + ii) * kTileStride, s_D + (wave * PW + ii + 1) * kTileStride, upad, lane);
         }
-        __syncthreads();
+        // A logit that is not finite means a source row of this group (or a reference pixel) holds a NaN or an Inf.  The GEMM
+        // below multiplies EVERY pixel of the group with EVERY row of the group's row set -- B is 0 for a row the pixel does not
+        // tap, and 0 x NaN = NaN --, so the value would reach pixels whose samples never touch it; the reference confines it to
+        // the pixels that tap it (include/epipolar_amd.h, "Non-finite values").  Such a group is split like one whose row set
+        // overflows, down to single pixels: a pixel's row set is its own taps, B has no zeros against foreign rows.  Every row
+        // of the row set is tapped by some pixel of the group (zero weights included: their products are in the logit), so no
+        // non-finite row escapes the test.  Block-uniform; the outputs this pass has already stored are stored again.
+        if (__syncthreads_or(odd_logit) && gsize > 1) return false;
 
         // ================= phase 3: out = B . F2_U on the matrix cores =================
         if (split_out) {
@@ -513,7 +530,7 @@ __device__ __forceinline__ void fwd_tile_body(const TileParams &tp, const int vb
             // K loop over pairs of rows, in groups of kG pairs; a group's operands (one LDS read and one
             // 8-byte load per MFMA pair) are requested a whole group (2 * kG MFMAs) ahead of their use.
             // Output column n of accumulator t is channel c0 + 2n + t: one float2 feeds both MFMAs.
-            // Columns U .. upad-1 of the B rows are zero and s_rows is padded with a valid row up to upad, so
+            // Columns U .. upad-1 of the B rows are zero and s_rows is padded up to upad with a row that reads zeros, so
             // the loop needs no bounds logic; rows of pixels outside this group hold stale values, but their
             // accumulator rows are never stored.
             constexpr int kG = 8;

@@ -961,7 +961,7 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
                     }
                 }
                 const int upad = (U + 15) & ~15;
-                if (lane < upad - U) rows[U + lane] = 0;
+                if (lane < upad - U) rows[U + lane] = kTilePadRow;
             }
             if (lane == 0) s2_publish(j, slot, fits, U);
             return;
@@ -993,7 +993,7 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
             // G2 walks the rows in groups of 16: pad the list with row 0 of the source map (a valid address; the
             // matching B columns are zero)
             const int upad = (U + 15) & ~15;
-            if (lane < upad - U) rows[U + lane] = 0;
+            if (lane < upad - U) rows[U + lane] = kTilePadRow;
         }
         if (lane == 0) s2_publish(j, slot, fits, U);
     };

@@ -45,7 +45,7 @@ __device__ __forceinline__ void softmax_grad(const BwdParams &p, int n, int pix,
             if (s * kWave + lane < K) v_da[s] += ga[(size_t)(s * kWave + lane) * HW];
     }
     if (d.softmax_enabled) {
-        float mx = neg_inf;
+        float mx = neg_inf;      // (fmaxf drops a NaN logit; expf(NaN - mx) below is NaN and reaches the sum and every weight)
 #pragma unroll
         for (int s = 0; s < KPL; ++s) mx = fmaxf(mx, (s * kWave + lane < K) ? v_logit[s] : neg_inf);
         mx = wave_max(mx);
@@ -100,30 +100,23 @@ __device__ __forceinline__ void write_res_base(const FwdParams &p, size_t row, i
     }
 }
 
-// First maximum over k (torch.argmax) of a[s] = value of sample s * 64 + lane: value, then lowest index.
+// First maximum over k (torch.argmax) of a[s] = value of sample s * 64 + lane: a NaN above every value, then the value, then
+// the lowest index (argmax_key).  Always one of the samples 0 .. K-1: the callers read a lane and p.steps[] with it.
 template <int KPL>
 __device__ __forceinline__ int first_argmax(const float (&a)[KPL], int K, int lane)
 {
-    float bestv = -__builtin_huge_valf();
+    unsigned bestk = 0u;
     int besti = 0x7fffffff;
 #pragma unroll
     for (int s = 0; s < KPL; ++s) {
         const int k = s * kWave + lane;
-        if (k < K && (a[s] > bestv)) {
-            bestv = a[s];
+        const unsigned key = argmax_key(a[s]);
+        if (k < K && key > bestk) {      // (ascending k: an equal key keeps the lower index)
+            bestk = key;
             besti = k;
         }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float ov = __shfl_xor(bestv, m);
-        const int oi = __shfl_xor(besti, m);
-        if (ov > bestv || (ov == bestv && oi < besti)) {
-            bestv = ov;
-            besti = oi;
-        }
-    }
-    return besti;
+    return wave_first_argmax(bestk, besti);
 }
 
 // The block's [K][16] attention tile in LDS -> (N,K,H,W): for a fixed k the 16 pixels of this block are contiguous.

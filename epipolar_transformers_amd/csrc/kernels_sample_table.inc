@@ -9,7 +9,11 @@
 //   off[r]  byte offset of the source row routed to tap register r (-1: none)
 //   w[r]    its bilinear weight (0 for out-of-image taps and for k >= K)
 //   need    bit r set when register r does not already hold that row, i.e.
-//           the previous sample's tap r was a different row
+//           the previous sample's tap r was a different row -- or when the tap
+//           is absent and the previous one was not: the register is then
+//           CLEARED (tap_row_* below), because its weight 0 times a stale row
+//           that holds a NaN or an Inf would be NaN, where the reference's zero
+//           padding contributes nothing
 template <int KPL>
 struct SampleTable {
     int off[KPL][4];
@@ -42,9 +46,19 @@ __device__ __forceinline__ void build_sample_table(const EtLayerDesc &d, const e
                 const int carry = __shfl(t.off[s > 0 ? s - 1 : 0][r], kWave - 1);
                 if (lane == 0) prev = carry;
             }
-            if (off >= 0 && off != prev) need |= 1 << r;
+            if (off != prev) need |= 1 << r;
         }
         t.need[s] = need;
     }
 }
 
+
+// Register r of a needed tap: the source row at byte offset `off` (wave-uniform), or zeros for an absent tap (off < 0).
+__device__ __forceinline__ float4 tap_row_f4(__amdgpu_buffer_rsrc_t src, int voff, int off)
+{
+    return off >= 0 ? buf_load_f4(src, voff, off) : f4_zero();
+}
+__device__ __forceinline__ float tap_row_f1(__amdgpu_buffer_rsrc_t src, int voff, int off)
+{
+    return off >= 0 ? buf_load_f1(src, voff, off) : 0.f;
+}

@@ -1,10 +1,16 @@
 // Included inside the anonymous namespace of a tile translation unit: the device helpers the one-block-per-tile forward
 // (kernels_forward_tile.inc) and the tiled backward (kernels_backward_tile.inc) share -- a sample's taps, building an array
 // row without LDS atomics, and the tile GEMMs (exact fp32 and split fp16).
+
 #pragma once
 #include "kernels_tile_order.inc"   // kTilePix, kTileRows*
 #include "et_wave_reduce.h"
 #include "et_split_f16.h"
+
+// Row index that pads a tile's row list up to the GEMMs' step: its byte offset, kTilePadRow * 1024 (+ the lane's channels), lies
+// past every map, so the raw buffer loads of a pad row return zeros.  (The forward's lists used to be padded with source row 0
+// against zero B columns: 0 x a NaN or an Inf in source pixel (0, 0) is NaN, in every pixel of the tile.)
+constexpr int kTilePadRow = 0x7ffff000 / 1024;
 
 // The four bilinear taps of a sample from its normalised location: the same arithmetic (and
 // rounding) as the tail of et::sample_setup, in plain nw / ne / sw / se order.
@@ -365,6 +371,8 @@ __device__ __forceinline__ bool tile_gemm_rows_split(const __amdgpu_buffer_rsrc_
                 for (int r = 0; r < 4; ++r) drow[(16 * g + r) * STRIDE + 16 * hh] = (acc[q][g][hh][r] * ai[g][r]) * inv_src;
             }
     }
+    // (an Inf trips this; a NaN is dropped by the running fmaxf and comes back as a NaN logit, which splits the tile down to
+    //  single pixels: fwd_tile_body, behind phase 2)
     return !(amax < kF16GuardLimit);
 }
 

@@ -140,7 +140,10 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const EtLayerDesc d, i
             for (int k = wave; k < 64; k += 16) {
                 const int pix = min(k * pstep, HW - 1);
                 const float4 v = map[(size_t)pix * (d.C >> 2) + (lane % (d.C >> 2))];
-                m[which] = fmaxf(m[which], fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+                // (a NaN or an Inf says nothing about the scale of the rest of the map: it counts as 0 here, and the tile that
+                //  holds it is redone in exact fp32 by the guards of the kernels that convert it)
+                auto mag = [](float x) { const float a = fabsf(x); return a <= kLargestFinite ? a : 0.f; };
+                m[which] = fmaxf(m[which], fmaxf(fmaxf(mag(v.x), mag(v.y)), fmaxf(mag(v.z), mag(v.w))));
             }
         }
     }

@@ -94,7 +94,31 @@ const char *et_last_error(void);
 int et_sample_locs(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
                    const float *cam, float *sample_locs, void *stream);
 
-/* Fused hot loop of Epipolar.forward in the headline mode (MERGE late,
+/* Non-finite values -- a NaN, +Inf or -Inf in feat_ref / feat_src / the maps of the general entry points, in grad_out or in a
+ * prior -- go through the attention operator as they go through the reference on the CPU (pinned to outputs of the reference
+ * itself: tests/golden/nonfinite/, tests/test_gpu_nonfinite.py).  The rule, for every entry point that says "non-finite: the
+ * rule" below:
+ *   never lost    where the reference's result is non-finite, so is ours.  The per-pixel kernels and the general kernels also
+ *                 return the same kind (NaN, +Inf, -Inf), forward and -- the per-pixel backward forms -- gradients; the tile
+ *                 kernels guarantee the finiteness only (a split-fp16 product turns Inf into NaN);
+ *   confined      where the reference's result is finite, ours is finite and as accurate as on finite inputs: a value spreads to
+ *                 the pixels whose bilinear taps include it (an in-image tap of weight 0 counts, as in F.grid_sample; a tap
+ *                 outside the image contributes nothing, whatever a register still holds) and no further.  The
+ *                 tile kernels multiply a whole tile with its whole row set, so a tile that meets a non-finite logit is
+ *                 processed pixel by pixel (the splitting path of an overflowing row set): slower, same result;
+ *   arg-max       corr_pos is torch.argmax's sample: a NaN ranks above every value and the first one wins -- a pixel whose
+ *                 weights are all NaN returns sample 0 --, then the value, then the lowest index.  Never an index outside
+ *                 the samples;
+ *   pair          a pair with finite inputs returns the same bits whatever another pair of the batch holds; no bit of the
+ *                 sticky error word is set.
+ * The tiled backward forms (et_epipolar_backward_tiled*, et_epipolar_backward_tiled_det*) keep "never lost" (finiteness) and
+ * "pair", not "confined to the pixel": their GEMMs contract over a tile's 32 pixels and its whole row set, and their operands are
+ * scaled by the tile's largest magnitude.  A non-finite value of feat_ref / feat_src / grad_out may therefore make non-finite, or
+ * (an Inf, through the scale) inaccurate, grad_ref of every pixel of the tiles that hold or tap it and grad_src of every source
+ * row those tiles tap -- entries of its OWN PAIR only.  Use the gather form for a step whose gradients may be non-finite and must
+ * stay confined.
+ *
+ * Fused hot loop of Epipolar.forward in the headline mode (MERGE late,
  * ATTENTION avg, SIMILARITY dot): epipolar.py:178-247 + epipolar_similarity
  * (272-321) + de_normalize (multiview.py:39-57), never materialising
  * sample_locs or the K x C x H x W sampled tensor.
@@ -105,7 +129,8 @@ int et_sample_locs(const EtLayerDesc *desc, const float *xs, const float *ys, co
  *   res_base  nullable : (N,H,W,C)  feat_ref + res_bias[c] (res_bias nullable = 0): the additive
  *                        term of the residual fusion, written while the reference row is in
  *                        registers.  With eval-mode BN folded into z, `ret + feat` (resnet.py:388,
- *                        epipolar.py:250-253) is then ONE GEMM:  x = res_base + (I + W') out . */
+ *                        epipolar.py:250-253) is then ONE GEMM:  x = res_base + (I + W') out.
+ * Non-finite: the rule (above), kinds included. */
 int et_epipolar_forward(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
                         const float *cam, const float *feat_ref, const float *feat_src, float *out,
                         float *attn, float *corr_pos, const float *res_bias, float *res_base,
@@ -157,7 +182,10 @@ int et_epipolar_forward(const EtLayerDesc *desc, const float *xs, const float *y
  *                   et_epipolar_forward_workspace_stats_offset(desc) bytes in, in tile order
  *                   (pair-major), readable by the caller after the call.
  * et_epipolar_forward_workspace_bytes returns 0 when the tile path does not apply to `desc`
- * (then et_epipolar_forward_tiled fails and et_epipolar_forward is the path to call). */
+ * (then et_epipolar_forward_tiled fails and et_epipolar_forward is the path to call).
+ * Non-finite: the rule (head of this section), finiteness only.  The persistent kernel's fp16 guard lists a tile whose first GEMM
+ * is not finite, the one-block-per-tile kernel redoes it in exact fp32 and, on a non-finite logit, pixel by pixel; the per-pair
+ * scale estimate skips NaN / Inf, so the rest of that pair's map keeps its precision. */
 size_t et_epipolar_forward_workspace_bytes(const EtLayerDesc *desc);
 size_t et_epipolar_forward_workspace_stats_offset(const EtLayerDesc *desc);
 size_t et_epipolar_forward_workspace_error_offset(const EtLayerDesc *desc);
@@ -182,7 +210,9 @@ int et_epipolar_forward_tiled(const EtLayerDesc *desc, const float *xs, const fl
  *              unpooled list (epipolar.py:237-242).
  * ATTENTION avg | max, SIMILARITY dot | cos | prior; FIND_CORR rgb is q = ref1, map_sim = ref2 (3 channels); soft-max on or off
  * as `desc` says; desc->C is ignored
- * (c_sim <= 512, c_val <= 4096, any positive value).  Nothing of size K x C x H x W is materialised. */
+ * (c_sim <= 512, c_val <= 4096, any positive value).  Nothing of size K x C x H x W is materialised.
+ * Non-finite: the rule (head of this section), kinds included: POOLING takes torch.max's maximum (a NaN wins over every value,
+ * of two NaNs the first), the arg-max of ATTENTION max and of corr_pos is torch.argmax's. */
 #define ET_GENERAL_POOLING 1
 #define ET_GENERAL_PRIOR_MUL 2
 #define ET_GENERAL_COSINE 4          /* SIMILARITY cos: F.cosine_similarity(q, sample) (epipolar.py:290-293), then mask / prior / soft-max as for dot */
@@ -212,7 +242,9 @@ int et_epipolar_forward_general(const EtLayerDesc *desc, const float *xs, const 
  *     under the `sim == 0` mask either way; SIMILARITY prior: grad_prior_k' = e_k' + ga_k';
  *   ATTENTION max: the attention is the raw cosine, so d sim_k' = ga_k' (no mask) goes through the cosine derivative into grad_q
  *     and grad_map_sim (both zero without grad_attn); with SIM_PRIOR beside it grad_prior_k' = ga_k'.  The value gradient is unchanged.
- * grad_out stays required (a loss on the attention alone passes zeros); grad_attn NULL = et_epipolar_backward_general, bit for bit. */
+ * grad_out stays required (a loss on the attention alone passes zeros); grad_attn NULL = et_epipolar_backward_general, bit for bit.
+ * Non-finite: the rule (head of this section); the map gradients arrive through float atomics, pairs with finite inputs agree to
+ * rounding.  Where nothing flows through the similarity (every mode but the cosine) q does not enter grad_q: a NaN in q stays out. */
 int et_epipolar_backward_general(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
                                  const float *cam, const float *q, const float *map_sim, const float *map_val,
                                  const float *prior, const float *grad_out, int c_sim, int c_val, int flags, float *grad_q,
@@ -235,7 +267,8 @@ int et_epipolar_backward_general_ga(const EtLayerDesc *desc, const float *xs, co
  *               one wave per source pixel sums alpha*g_p + beta*f_p in ascending p):
  *               no float atomics, bit-reproducible.  With NULL (or variant bit
  *               ET_VARIANT_BWD_ATOMIC) grad_src is zero-filled and accumulated with
- *               float atomics (bilinear-transpose scatter, run-to-run rounding noise). */
+ *               float atomics (bilinear-transpose scatter, run-to-run rounding noise).
+ * Non-finite: the rule (head of this section), both forms, kinds included. */
 size_t et_epipolar_backward_workspace_bytes(const EtLayerDesc *desc);
 int et_epipolar_backward(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
                          const float *cam, const float *feat_ref, const float *feat_src,
@@ -299,9 +332,11 @@ int et_epipolar_backward_tiled_ga(const EtLayerDesc *desc, const float *xs, cons
  *   workspace : et_epipolar_backward_tiled_det_workspace_bytes(desc) bytes (0 exactly where the tiled form's is 0): the
  *               forward-layout workspace -- same 64-word header, same rules (zero-initialised once; any base alignment; may be
  *               shared with the other tile calls on one stream) -- followed by the int64 accumulator (N H W 256 x 8 bytes), the
- *               pairs' quanta and maxima, all written before they are read.  Sticky error word, bit 2 (value 4): a contribution
- *               of 2^48 quanta or more (or a NaN / inf) was met and NOT added -- impossible for finite inputs under the bound;
- *               the results of that call are invalid.
+ *               pairs' quanta and maxima, all written before they are read.  Sticky error word, bit 2 (value 4): a FINITE
+ *               contribution of 2^48 quanta or more was met and NOT added -- impossible under the bound; the results of that
+ *               call are invalid.
+ * Non-finite: the tiled rule (head of this section).  The maxima skip NaN / Inf, so the pair's finite values keep their quantum; a
+ * contribution that is NaN or infinite marks its accumulator element, which comes out NaN -- no error bit, same bits run after run.
  * Fails (et_last_error) with the soft-max off (the "attention" sim / K has no bound: et_epipolar_backward with a workspace is the
  * bit-reproducible form there), on a workspace that is too small, and where the tile path does not apply.
  * et_debug_host_det_quantum: HOST test hook, no GPU -- q and the bound for given maxima (desc: softmax_scale).
@@ -328,7 +363,8 @@ int et_debug_host_det_quantum_ga(const EtLayerDesc *desc, float m_ref, float m_s
  * y = z(out) is the 1x1-conv (GEMM) result, scale/shift = batch-norm affine
  * folded with its (running or batch) statistics.  y/scale/shift may be NULL
  * for the un-parameterised layer (x = feat + out).  finalout nullable:
- * receives out + y*scale + shift (what Epipolar.forward returns).  All (N,H,W,C). */
+ * receives out + y*scale + shift (what Epipolar.forward returns).  All (N,H,W,C).
+ * Non-finite: element by element, as IEEE arithmetic has it. */
 int et_residual_epilogue(int64_t num_pixels, int32_t C, const float *feat, const float *out,
                          const float *y, const float *scale, const float *shift, float *finalout,
                          float *x, void *stream);
@@ -340,7 +376,9 @@ int et_residual_epilogue(int64_t num_pixels, int32_t C, const float *feat, const
  * split-fp16 MFMAs with fp32 accumulation (fp32-level error; every row of `out` is scaled by its own power of
  * two).  et_residual_gemm_pack lays Wf out for the kernel into `packed` (et_residual_gemm_packed_bytes() bytes,
  * 16-byte aligned; repack when the weights change).  feat nullable (then x = bias + out . Wf^T, what
- * Epipolar.forward returns).  out / feat / x: (num_pixels, 256) fp32, x may not alias out or feat. */
+ * Epipolar.forward returns).  out / feat / x: (num_pixels, 256) fp32, x may not alias out or feat.
+ * Non-finite: a row of `out` that holds a NaN / Inf gives a non-finite row of x; every other row -- those of its 32-row block
+ * included -- is computed as on finite inputs. */
 size_t et_residual_gemm_packed_bytes(void);
 int et_residual_gemm_pack(const float *wf, void *packed, void *stream);
 int et_residual_gemm(int64_t num_pixels, int32_t C, const float *out, const float *feat, const void *packed,
@@ -397,7 +435,8 @@ int et_z_wgrad(int64_t num_pixels, int32_t C, const float *grad_y, const float *
  *   out_scratch : (N,H,W,256), required: the rows of tiles the persistent kernel hands to its overflow list (a row set
  *                 beyond its arrays, a source value beyond fp16's range) are produced there by the one-block-per-tile
  *                 kernel and their x rows by a small follow-up kernel; with want_out != 0 every row of `out` is written.
- *   workspace   : as et_epipolar_forward_tiled (same size, same sticky error word). */
+ *   workspace   : as et_epipolar_forward_tiled (same size, same sticky error word).
+ * Non-finite: the rule (head of this section), finiteness only; the tile that meets the value goes to the overflow follow-up. */
 int et_epipolar_forward_fused(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
                               const float *cam, const float *feat_ref, const float *feat_src, const void *packed_w,
                               const float *bias, float *x, float *attn, float *corr_pos, float *out_scratch,
