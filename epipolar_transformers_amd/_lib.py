@@ -96,6 +96,10 @@ _SIGNATURES = {
                                         ctypes.c_float, ctypes.c_int32, _P, _P, _P]),
     "et_debug_host_heatmap_peaks": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_float, ctypes.c_float,
                                                    ctypes.c_float, ctypes.c_int32, _P, _P]),
+    "et_heatmap_peaks_bwd": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_float, ctypes.c_float,
+                                            ctypes.c_float, ctypes.c_int32, _P, _P, _P, _P]),
+    "et_debug_host_heatmap_peaks_bwd": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_float,
+                                                       ctypes.c_float, ctypes.c_float, ctypes.c_int32, _P, _P, _P]),
     "et_triangulate_epipolar": (ctypes.c_int, [ctypes.c_int32] * 5 + [_P] * 5 + [ctypes.c_float] * 2 + [ctypes.c_double] * 2 +
                                 [ctypes.c_int32, _P, _P, _P]),
     "et_debug_host_triangulate_epipolar": (ctypes.c_int, [ctypes.c_int32] * 5 + [_P] * 5 + [ctypes.c_float] * 2 +

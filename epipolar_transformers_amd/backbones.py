@@ -129,14 +129,22 @@ def soft_argmax_peaks(heatmaps: torch.Tensor, radius: float, downsample: int, th
     return torch.stack([x, y], 1).view(n, j, 2), score.view(n, j)
 
 
-def find_peaks(heatmaps: torch.Tensor, radius: float, downsample: float, legacy_floor_division: bool = False):
+def find_peaks(heatmaps: torch.Tensor, radius: float, downsample: float, legacy_floor_division: bool = False, grad: bool = False):
     """Peak finder of the head: the fused HIP kernel (ops.heatmap_peaks, one launch) for float32 heat maps on the GPU,
-    the batched torch restatement (soft_argmax_peaks) otherwise (CPU plumbing runs of the single-view net)."""
+    the batched torch restatement (soft_argmax_peaks) otherwise (CPU plumbing runs of the single-view net).
+    `grad` (EPIPOLAR_AMD.PEAK_GRAD): the kernel route returns locations and scores that are differentiable in the maps, as the
+    reference's are (ops.heatmap_peaks(with_grad=True)); without it that route returns them detached.  The torch route is plain
+    autograd either way."""
     if heatmaps.is_cuda and heatmaps.dtype == torch.float32:
         from . import ops
 
-        return ops.heatmap_peaks(heatmaps, radius, downsample, legacy_floor_division=legacy_floor_division)
+        return ops.heatmap_peaks(heatmaps, radius, downsample, legacy_floor_division=legacy_floor_division, with_grad=grad)
     return soft_argmax_peaks(heatmaps, radius, downsample, legacy_floor_division=legacy_floor_division)
+
+
+def peak_grad(cfg) -> bool:
+    """EPIPOLAR_AMD.PEAK_GRAD: the detections a forward returns carry gradient back into the heat map."""
+    return bool(amd_knob(cfg, "PEAK_GRAD", False))
 
 
 class PoseResNet(nn.Module):
@@ -235,7 +243,7 @@ class PoseResNet(nn.Module):
         else:
             x = feature
         heatmap = self.final_layer(x)
-        locs, scos = find_peaks(heatmap, self.cfg.KEYPOINT.SIGMA, self.cfg.BACKBONE.DOWNSAMPLE)
+        locs, scos = find_peaks(heatmap, self.cfg.KEYPOINT.SIGMA, self.cfg.BACKBONE.DOWNSAMPLE, grad=peak_grad(self.cfg))
         if other_features is None:
             corr_pos, depth = None, None
         return feature, [heatmap], locs, scos, corr_pos, depth, sample_locs, None

@@ -193,7 +193,10 @@ def default_cfg() -> CfgNode:
                                               # (ET_VARIANT_BWD_DETERMINISTIC); option branches raise on backward instead
     C.EPIPOLAR_AMD.ATTN_GRAD = False          # True: the `depth` (attention) Epipolar.forward returns carries gradient, as in the
                                               # reference (epipolar.py:245, 263) -- a loss on it trains the features (HIP kernels)
-    C.EPIPOLAR_AMD.FUSED_EPILOGUE = True      # eval: fold BN and fuse the residual adds in one kernel
+    C.EPIPOLAR_AMD.PEAK_GRAD = False          # True: the `batch_locs` / `batch_scos` a forward returns carry gradient into the heat map, as in
+                                              # the reference (basic_batch.py:17-63 runs outside no_grad) -- a loss on the key points trains the
+                                              # network (HIP kernel et_heatmap_peaks_bwd; bit-reproducible)
+    C.EPIPOLAR_AMD.FUSED_EPILOGUE = True     # eval: fold BN and fuse the residual adds in one kernel
     C.EPIPOLAR_AMD.SHARD_P2P = False          # view-sharded partition: source maps by one all-to-all (each block to the rank that
                                               # samples it) instead of the all-gather BASELINE.json's north star names (G x the bytes)
     C.EPIPOLAR_AMD.LIFT_KERNELS = False       # True: KEYPOINT.TRIANGULATION pymvg / naive / refine lift through their HIP kernels

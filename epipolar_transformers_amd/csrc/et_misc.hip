@@ -5,7 +5,7 @@
 thread_local char et_g_err[512] = "";
 
 namespace {
-#include "kernels_misc.inc"      // sample_locs_kernel, residual_epilogue_kernel, transpose_kernel, heatmap_peaks_kernel
+#include "kernels_misc.inc"      // sample_locs_kernel, residual_epilogue_kernel, transpose_kernel, heatmap_peaks_kernel, heatmap_peaks_bwd_kernel
 
 // the argument checks et_heatmap_peaks and its host hook share
 int check_peaks(const char *what, int64_t num_maps, int32_t H, int32_t W, const float *heatmaps, float radius, const float *locs,
@@ -16,6 +16,15 @@ int check_peaks(const char *what, int64_t num_maps, int32_t H, int32_t W, const 
     // int(radius + 0.5) >= 1 (the ramp's step divides by it); the upper end keeps the window's pixel arithmetic finite
     if (!(radius > 0.f) || !(radius <= 4096.f) || (int)(radius + 0.5f) < 1) return fail("%s: radius %g outside [0.5, 4096]", what, radius);
     if (!heatmaps || !locs || !scores) return fail("%s: NULL pointer", what);
+    return 0;
+}
+
+// ... and those of et_heatmap_peaks_bwd and its host hook: the forward's, with the output and at least one incoming gradient
+int check_peaks_bwd(const char *what, int64_t num_maps, int32_t H, int32_t W, const float *heatmaps, float radius, const float *grad_locs,
+                    const float *grad_scores, const float *grad_heat)
+{
+    if (int e = check_peaks(what, num_maps, H, W, heatmaps, radius, grad_heat, grad_heat)) return e;
+    if (!grad_locs && !grad_scores) return fail("%s: grad_locs and grad_scores are both NULL", what);
     return 0;
 }
 }  // namespace
@@ -122,6 +131,28 @@ int et_debug_host_heatmap_peaks(int64_t num_maps, int32_t H, int32_t W, const fl
     for (int64_t m = 0; m < num_maps; ++m)
         et_peaks::host_peak(heatmaps + (size_t)m * H * W, H, W, radius, downsample, threshold, legacy_floor_division, locs + 2 * m,
                             scores + m);
+    return 0;
+}
+
+int et_heatmap_peaks_bwd(int64_t num_maps, int32_t H, int32_t W, const float *heatmaps, float radius, float downsample, float threshold,
+                         int32_t legacy_floor_division, const float *grad_locs, const float *grad_scores, float *grad_heat, void *stream)
+{
+    if (int e = check_peaks_bwd("et_heatmap_peaks_bwd", num_maps, H, W, heatmaps, radius, grad_locs, grad_scores, grad_heat)) return e;
+    hipLaunchKernelGGL(heatmap_peaks_bwd_kernel, dim3((unsigned)num_maps), dim3(et_peaks::kThreads), 0, (hipStream_t)stream, heatmaps, H,
+                       W, radius, downsample, threshold, legacy_floor_division, grad_locs, grad_scores, grad_heat);
+    return check_launch("et_heatmap_peaks_bwd");
+}
+
+int et_debug_host_heatmap_peaks_bwd(int64_t num_maps, int32_t H, int32_t W, const float *heatmaps, float radius, float downsample,
+                                    float threshold, int32_t legacy_floor_division, const float *grad_locs, const float *grad_scores,
+                                    float *grad_heat)
+{
+    if (int e = check_peaks_bwd("et_debug_host_heatmap_peaks_bwd", num_maps, H, W, heatmaps, radius, grad_locs, grad_scores, grad_heat))
+        return e;
+    for (int64_t m = 0; m < num_maps; ++m)
+        et_peaks::host_peak_bwd(heatmaps + (size_t)m * H * W, H, W, radius, downsample, threshold, legacy_floor_division,
+                                grad_locs ? grad_locs + 2 * m : nullptr, grad_scores ? grad_scores + m : nullptr,
+                                grad_heat + (size_t)m * H * W);
     return 0;
 }
 

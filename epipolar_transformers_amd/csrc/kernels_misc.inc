@@ -86,18 +86,12 @@ __global__ __launch_bounds__(256) void transpose_kernel(int rows, int cols, cons
 //      then pix2coord (x * downsample + downsample / 2 - 0.5).
 // The arithmetic of one map is et_peaks.h's (shared with the host hook); here: the block's reduction layout.
 // ----------------------------------------------------------------------------
-__global__ __launch_bounds__(et_peaks::kThreads) void heatmap_peaks_kernel(const float *__restrict__ heat, int H, int W, float radius,
-                                                                            float downsample, float threshold, int legacy_floor,
-                                                                            float *__restrict__ locs, float *__restrict__ scores)
+// arg-max of one map by the block (NaN above every value, then the value, then the lowest index: et_peaks.h); every thread returns
+// the raw index (et_peaks::kNoCandidate for a map without a candidate) and the score
+__device__ __forceinline__ int peaks_block_argmax(const float *__restrict__ hm, int HW, float *s_val, int *s_idx, float &score)
 {
     constexpr int kThreads = et_peaks::kThreads;
-    __shared__ float s_val[kThreads];
-    __shared__ int s_idx[kThreads];
-    __shared__ float s_acc[3][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float *hm = heat + (size_t)blockIdx.x * H * W;
-    const int HW = H * W;
-    // ---- 1. arg-max (NaN above every value, then the value, then the lowest index: et_peaks.h) ----
+    const int tid = threadIdx.x;
     float best = -__builtin_huge_valf();
     int bidx = et_peaks::kNoCandidate;
     for (int i = tid; i < HW; i += kThreads) {
@@ -121,11 +115,17 @@ __global__ __launch_bounds__(et_peaks::kThreads) void heatmap_peaks_kernel(const
         }
         __syncthreads();
     }
-    const float score = s_val[0];
-    // ---- 2. / 3. the resampled window ----
-    const et_peaks::Window win = et_peaks::make_window(et_peaks::resolve_index(s_idx[0]), H, W, radius, threshold, legacy_floor);
+    score = s_val[0];
+    return s_idx[0];
+}
+
+// the three sums of the resampled window by the block: per-wave totals in s_acc[k][wave], valid after the barrier at the end;
+// the block's totals are (s_acc[k][0] + s_acc[k][1]) + (s_acc[k][2] + s_acc[k][3])
+__device__ __forceinline__ void peaks_block_sums(const float *__restrict__ hm, int H, int W, const et_peaks::Window &win, float (*s_acc)[4])
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float sum = 0.f, sx = 0.f, sy = 0.f;
-    for (int e = tid; e < win.side * win.side; e += kThreads) {
+    for (int e = tid; e < win.side * win.side; e += et_peaks::kThreads) {
         float rx, ry;
         const float v = et_peaks::window_sample(hm, H, W, win, e, rx, ry);
         sum += v;
@@ -143,13 +143,83 @@ __global__ __launch_bounds__(et_peaks::kThreads) void heatmap_peaks_kernel(const
         s_acc[2][wave] = sy;
     }
     __syncthreads();
-    if (tid == 0) {
+}
+
+__global__ __launch_bounds__(et_peaks::kThreads) void heatmap_peaks_kernel(const float *__restrict__ heat, int H, int W, float radius,
+                                                                            float downsample, float threshold, int legacy_floor,
+                                                                            float *__restrict__ locs, float *__restrict__ scores)
+{
+    constexpr int kThreads = et_peaks::kThreads;
+    __shared__ float s_val[kThreads];
+    __shared__ int s_idx[kThreads];
+    __shared__ float s_acc[3][4];
+    const float *hm = heat + (size_t)blockIdx.x * H * W;
+    // ---- 1. arg-max ----
+    float score;
+    const int index = peaks_block_argmax(hm, H * W, s_val, s_idx, score);
+    // ---- 2. / 3. the resampled window ----
+    const et_peaks::Window win = et_peaks::make_window(et_peaks::resolve_index(index), H, W, radius, threshold, legacy_floor);
+    peaks_block_sums(hm, H, W, win, s_acc);
+    if (threadIdx.x == 0) {
         float x, y;
         et_peaks::finish((s_acc[0][0] + s_acc[0][1]) + (s_acc[0][2] + s_acc[0][3]), (s_acc[1][0] + s_acc[1][1]) + (s_acc[1][2] + s_acc[1][3]),
                          (s_acc[2][0] + s_acc[2][1]) + (s_acc[2][2] + s_acc[2][3]), win, downsample, x, y);
         locs[(size_t)blockIdx.x * 2] = x;
         locs[(size_t)blockIdx.x * 2 + 1] = y;
         scores[blockIdx.x] = score;
+    }
+}
+
+// ----------------------------------------------------------------------------
+// The peak finder's backward: d(locs), d(scores) -> d(heat map), one block per map, the forward's index, window and sums
+// recomputed by the forward's own block routines.  Gather form (et_peaks.h, cell_grad): every cell of the map is written by exactly
+// one thread -- 0 outside the window's clipped footprint, inside it the sum over the elements that tap the cell in ascending
+// element order, plus d(score) on the arg-max cell -- so there are no atomics and the bits do not depend on the batch.
+// grad_locs / grad_scores may be NULL (not both): without d(locs) the window is not visited at all.
+// ----------------------------------------------------------------------------
+__global__ __launch_bounds__(et_peaks::kThreads) void heatmap_peaks_bwd_kernel(const float *__restrict__ heat, int H, int W, float radius,
+                                                                                float downsample, float threshold, int legacy_floor,
+                                                                                const float *__restrict__ grad_locs,
+                                                                                const float *__restrict__ grad_scores,
+                                                                                float *__restrict__ grad_heat)
+{
+    constexpr int kThreads = et_peaks::kThreads;
+    __shared__ float s_val[kThreads];
+    __shared__ int s_idx[kThreads];
+    __shared__ float s_acc[3][4];
+    const int tid = threadIdx.x;
+    const float *hm = heat + (size_t)blockIdx.x * H * W;
+    float *grad = grad_heat + (size_t)blockIdx.x * H * W;
+    const int HW = H * W;
+    float score;
+    const int index = et_peaks::resolve_index(peaks_block_argmax(hm, HW, s_val, s_idx, score));
+    const bool has_score = grad_scores != nullptr;
+    const float g_score = has_score ? grad_scores[blockIdx.x] : 0.f;
+    int x0 = 0, x1 = -1, y0 = 0, y1 = -1;                           // the footprint; empty without d(locs)
+    if (grad_locs) {
+        const et_peaks::Window win = et_peaks::make_window(index, H, W, radius, threshold, legacy_floor);
+        peaks_block_sums(hm, H, W, win, s_acc);
+        const et_peaks::GradCoef coef = et_peaks::make_coef(
+            (s_acc[0][0] + s_acc[0][1]) + (s_acc[0][2] + s_acc[0][3]), (s_acc[1][0] + s_acc[1][1]) + (s_acc[1][2] + s_acc[1][3]),
+            (s_acc[2][0] + s_acc[2][1]) + (s_acc[2][2] + s_acc[2][3]), grad_locs[(size_t)blockIdx.x * 2], grad_locs[(size_t)blockIdx.x * 2 + 1],
+            downsample);
+        et_peaks::footprint(win.t00, win.t02, win.side, W, x0, x1);
+        et_peaks::footprint(win.t11, win.t12, win.side, H, y0, y1);
+        // the footprint's cells, one per thread and trip: x0 <= x <= x1 <= W - 1, y0 <= y <= y1 <= H - 1
+        const int fw = x1 - x0 + 1, fh = y1 - y0 + 1;
+        if (fw > 0 && fh > 0)
+            for (int c = tid; c < fw * fh; c += kThreads) {
+                const int y = y0 + c / fw, x = x0 + c % fw;
+                const int i = y * W + x;
+                const float g = et_peaks::cell_grad(hm, H, W, win, coef, y, x);
+                grad[i] = (has_score && i == index) ? g + g_score : g;
+            }
+    }
+    // every other cell (an empty footprint, x1 < x0 or y1 < y0, holds none)
+    for (int i = tid; i < HW; i += kThreads) {
+        const int y = i / W, x = i - y * W;
+        if (x >= x0 && x <= x1 && y >= y0 && y <= y1) continue;
+        grad[i] = (has_score && i == index) ? 0.f + g_score : 0.f;
     }
 }
 

@@ -22,7 +22,7 @@ import torch
 from torch import nn
 import torch.nn.functional as F
 
-from .backbones import BACKBONES, find_peaks
+from .backbones import BACKBONES, find_peaks, peak_grad
 from .config import get_cfg
 from .epipolar import Epipolar
 
@@ -173,7 +173,7 @@ class HourGlassPoseNet(nn.Module):
             heatmaps.append(heat)
             if i < self.nStack - 1:
                 x = x + self.trsfeas[i](feature) + self.trstmps[i](heat)
-        locs, scos = find_peaks(heatmaps[-1], self.sigma, self.downsample)
+        locs, scos = find_peaks(heatmaps[-1], self.sigma, self.downsample, grad=peak_grad(self.cfg))
         if other_features is None:
             corr_pos, depth = None, None
         else:

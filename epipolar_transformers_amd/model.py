@@ -99,7 +99,7 @@ class MultiViewPoseModel(nn.Module):
             other = other.detach()
         x, corr_pos, depth, sample_locs = net._fuse(feature, net.epipolar_sampler, other, KRT, other_KRT, camera, other_camera)
         heatmap = net.final_layer(x)
-        locs, scos = backbones.find_peaks(heatmap, self.cfg.KEYPOINT.SIGMA, self.cfg.BACKBONE.DOWNSAMPLE)
+        locs, scos = backbones.find_peaks(heatmap, self.cfg.KEYPOINT.SIGMA, self.cfg.BACKBONE.DOWNSAMPLE, grad=backbones.peak_grad(self.cfg))
         return feature, [heatmap], locs, scos, corr_pos, depth, sample_locs, None
 
     def forward_views_sharded(self, img: torch.Tensor, KRT: torch.Tensor, other_KRT: torch.Tensor, camera=None,
@@ -127,7 +127,7 @@ class MultiViewPoseModel(nn.Module):
             other = other.detach()
         x, corr_pos, depth, sample_locs = net._fuse(feature, net.epipolar_sampler, other, KRT, other_KRT, camera, other_camera)
         heatmap = net.final_layer(x)
-        locs, scos = backbones.find_peaks(heatmap, self.cfg.KEYPOINT.SIGMA, self.cfg.BACKBONE.DOWNSAMPLE)
+        locs, scos = backbones.find_peaks(heatmap, self.cfg.KEYPOINT.SIGMA, self.cfg.BACKBONE.DOWNSAMPLE, grad=backbones.peak_grad(self.cfg))
         return feature, [heatmap], locs, scos, corr_pos, depth, sample_locs, None
 
     def forward_multitest(self, img: torch.Tensor, KRT: torch.Tensor, num_views: int):
@@ -184,7 +184,11 @@ class MultiViewPoseModel(nn.Module):
                                     refine (:425-441, 99-154, 162-232) run as HIP kernels (ops.triangulate_views, which states
                                     how the random pairs of naive / refine are enumerated) from the detections, scores and
                                     projections alone, so all three also work with EPIPOLAR.MULTITEST; rpsm without its dict
-                                    is pymvg, and an unknown name is a ValueError."""
+                                    is pymvg, and an unknown name is a ValueError.
+        Gradient: with EPIPOLAR_AMD.PEAK_GRAD the detections arrive attached to the heat maps (ops.heatmap_peaks(with_grad=True)),
+        and the default route -- the float64 torch DLT of triangulate.py, torch.linalg.svd -- differentiates in them, so a loss on
+        the lifted points reaches the network.  The HIP liftings (ops.triangulate_views, ops.triangulate_epipolar, ops.rpsm)
+        still return no gradient."""
         cfg = self.cfg
         m, j, _ = batch_locs.shape
         f = m // num_views

@@ -799,18 +799,55 @@ def z_wgrad(grad_y: torch.Tensor, out: torch.Tensor, workspace: torch.Tensor = N
     return gw, gb
 
 
-def heatmap_peaks(heatmaps: torch.Tensor, radius: float, downsample: float, threshold: float = 1e-6,
-                  legacy_floor_division: bool = False):
-    """find_tensor_peak_batch for a whole batch in ONE kernel: heatmaps (N,J,H,W) -> locations (N,J,2) in image
-    coordinates and scores (N,J).  No gradient (the reference's locations are only used for evaluation)."""
-    _require_gpu(heatmaps, "heatmaps")
-    n, j, h, w = heatmaps.shape
-    hm = heatmaps.detach().contiguous()
+def _heatmap_peaks(hm: torch.Tensor, radius: float, downsample: float, threshold: float, legacy: int):
+    n, j, h, w = hm.shape
     locs = _empty((n, j, 2), device=hm.device)
     scores = _empty((n, j), device=hm.device)
-    _call("et_heatmap_peaks", hm, n * j, h, w, _ptr(hm), float(radius), float(downsample), float(threshold),
-          int(bool(legacy_floor_division)), _ptr(locs), _ptr(scores), _stream(hm))
+    _call("et_heatmap_peaks", hm, n * j, h, w, _ptr(hm), radius, downsample, threshold, legacy, _ptr(locs), _ptr(scores), _stream(hm))
     return locs, scores
+
+
+class HeatmapPeaks(torch.autograd.Function):
+    """et_heatmap_peaks / et_heatmap_peaks_bwd.  Only the maps receive a gradient; an output nobody differentiated reaches the
+    library as NULL (its gradient is not materialised)."""
+
+    @staticmethod
+    def forward(ctx, hm, radius, downsample, threshold, legacy):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(hm)
+        ctx.call = (radius, downsample, threshold, legacy)
+        return _heatmap_peaks(hm, radius, downsample, threshold, legacy)
+
+    @staticmethod
+    def backward(ctx, grad_locs, grad_scores):
+        hm, = ctx.saved_tensors
+        if grad_locs is None and grad_scores is None:
+            return None, None, None, None, None
+        n, j, h, w = hm.shape
+        if grad_locs is not None:
+            grad_locs = grad_locs.to(torch.float32).contiguous()
+            _require_f32(grad_locs, "grad_locs", hm.device, (n, j, 2))
+        if grad_scores is not None:
+            grad_scores = grad_scores.to(torch.float32).contiguous()
+            _require_f32(grad_scores, "grad_scores", hm.device, (n, j))
+        grad = _empty(None, like=hm)
+        _call("et_heatmap_peaks_bwd", hm, n * j, h, w, _ptr(hm), *ctx.call, _ptr(grad_locs), _ptr(grad_scores), _ptr(grad), _stream(hm))
+        return grad, None, None, None, None
+
+
+def heatmap_peaks(heatmaps: torch.Tensor, radius: float, downsample: float, threshold: float = 1e-6,
+                  legacy_floor_division: bool = False, with_grad: bool = False):
+    """find_tensor_peak_batch for a whole batch in ONE kernel: heatmaps (N,J,H,W) -> locations (N,J,2) in image
+    coordinates and scores (N,J).
+    `with_grad` False (the default): both are detached.  True, and `heatmaps` requires a gradient: locations and scores are
+    differentiable in the maps as the reference's are (HeatmapPeaks: et_heatmap_peaks_bwd, one launch, no atomics, the same bits
+    from run to run and in any batch); index_w, index_h and the window's box are constants, as the reference takes .data of
+    them.  `radius`, `downsample` and `threshold` receive no gradient."""
+    _require_gpu(heatmaps, "heatmaps")
+    args = (float(radius), float(downsample), float(threshold), int(bool(legacy_floor_division)))
+    if with_grad and heatmaps.requires_grad and torch.is_grad_enabled():
+        return HeatmapPeaks.apply(heatmaps.contiguous(), *args)
+    return _heatmap_peaks(heatmaps.detach().contiguous(), *args)
 
 
 def triangulate_epipolar(pts: torch.Tensor, conf: torch.Tensor, krt: torch.Tensor, other_krt: torch.Tensor,

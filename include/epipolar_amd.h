@@ -462,6 +462,26 @@ int et_heatmap_peaks(int64_t num_maps, int32_t H, int32_t W, const float *heatma
 int et_debug_host_heatmap_peaks(int64_t num_maps, int32_t H, int32_t W, const float *heatmaps, float radius, float downsample,
                                 float threshold, int32_t legacy_floor_division, float *locs, float *scores);
 
+/* The peak finder's backward: the gradient find_tensor_peak_batch's autograd (F.grid_sample, F.threshold, the two weighted sums,
+ * torch.max) leaves in the heat maps.  One launch for all maps, no atomics, every sum in a fixed order: the same bits from run to
+ * run and whatever else the batch holds.  The leading arguments are et_heatmap_peaks's, on the same maps.
+ *   grad_locs   : (num_maps, 2) gradient of locs, or NULL ;  grad_scores : (num_maps) gradient of scores, or NULL (not both NULL)
+ *   grad_heat   : (num_maps, H, W), EVERY element written
+ * The index, the window and its three sums S, Sx, Sy are recomputed by the forward's own routines (csrc/et_peaks.h).  With
+ * tot = S + eps, window element e -- thresholded value v_e, ramps rx_e, ry_e -- receives
+ *   c_e = downsample (g_x (rx_e - Sx / tot) + g_y (ry_e - Sy / tot)) / tot   if the sample was kept (not <= threshold: a NaN is
+ * kept), else 0 -- evaluated as downsample (g_x (rx_e tot - Sx) + g_y (ry_e tot - Sy)) / tot / tot, which is exactly 0 where one
+ * sample alone survives the threshold and the location therefore does not depend on the map; each of its four bilinear taps inside the map receives c_e times the tap's weight; the arg-max cell (the first
+ * maximum) receives grad_scores on top; every other cell is 0.  index_w, index_h and the box are constants, as in the reference
+ * (.data).  With grad_locs NULL the window is not visited: a map with a NaN still returns the one finite grad_scores entry.
+ * et_debug_host_heatmap_peaks_bwd: HOST test hook, no GPU, the same per-cell routine and summation order; host pointers. */
+int et_heatmap_peaks_bwd(int64_t num_maps, int32_t H, int32_t W, const float *heatmaps, float radius, float downsample,
+                         float threshold, int32_t legacy_floor_division, const float *grad_locs, const float *grad_scores,
+                         float *grad_heat, void *stream);
+int et_debug_host_heatmap_peaks_bwd(int64_t num_maps, int32_t H, int32_t W, const float *heatmaps, float radius, float downsample,
+                                    float threshold, int32_t legacy_floor_division, const float *grad_locs,
+                                    const float *grad_scores, float *grad_heat);
+
 /* KEYPOINT.TRIANGULATION epipolar / epipolar_dlt: triangulate_epipolar (vision/triangulation.py:234-348), the lifting that
  * consumes the layer's corr_pos.  Every (frame, joint) is independent; inputs float32, all arithmetic float64.  One launch.
  *   pts       : (F, V, J, 2) image coordinates, already multiplied by resize = IMAGE_RESIZE * PREDICT_RESIZE
