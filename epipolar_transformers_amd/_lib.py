@@ -107,7 +107,9 @@ _SIGNATURES = {
     "et_triangulate_views": (ctypes.c_int, [ctypes.c_int32] * 3 + [_P] * 3 + [ctypes.c_int32] + [ctypes.c_double] * 2 + [_P, _P, _P]),
     "et_debug_host_triangulate_views": (ctypes.c_int, [ctypes.c_int32] * 3 + [_P] * 3 + [ctypes.c_int32] + [ctypes.c_double] * 2 +
                                         [_P, _P]),
-    "et_rpsm_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32] * 4),
+    "et_triangulate_bwd": (ctypes.c_int, [ctypes.c_int32] * 5 + [_P] * 4 + [ctypes.c_float] * 2 + [_P] * 4),
+    "et_debug_host_triangulate_bwd": (ctypes.c_int, [ctypes.c_int32] * 5 + [_P] * 4 + [ctypes.c_float] * 2 + [_P] * 3),
+    "et_rpsm_workspace_bytes":(ctypes.c_size_t, [ctypes.c_int32] * 4),
     "et_rpsm": (ctypes.c_int, [ctypes.c_int32] * 5 + [_P] * 7 + [ctypes.c_float] * 2 + [ctypes.c_double] + [ctypes.c_int32] * 3 +
                 [ctypes.c_float, ctypes.c_int32, _P, _P, _P, ctypes.c_size_t, _P]),
     "et_debug_host_rpsm": (ctypes.c_int, [ctypes.c_int32] * 5 + [_P] * 7 + [ctypes.c_float] * 2 + [ctypes.c_double] +

@@ -195,7 +195,9 @@ def default_cfg() -> CfgNode:
                                               # reference (epipolar.py:245, 263) -- a loss on it trains the features (HIP kernels)
     C.EPIPOLAR_AMD.PEAK_GRAD = False          # True: the `batch_locs` / `batch_scos` a forward returns carry gradient into the heat map, as in
                                               # the reference (basic_batch.py:17-63 runs outside no_grad) -- a loss on the key points trains the
-                                              # network (HIP kernel et_heatmap_peaks_bwd; bit-reproducible)
+                                              # network (HIP kernel et_heatmap_peaks_bwd; bit-reproducible).  MultiViewPoseModel.lift then carries
+                                              # it on to the 3-D points through every DLT lifting, the HIP ones included (et_triangulate_bwd);
+                                              # rpsm, a grid search, has no gradient
     C.EPIPOLAR_AMD.FUSED_EPILOGUE = True     # eval: fold BN and fuse the residual adds in one kernel
     C.EPIPOLAR_AMD.SHARD_P2P = False          # view-sharded partition: source maps by one all-to-all (each block to the rank that
                                               # samples it) instead of the all-gather BASELINE.json's north star names (G x the bytes)

@@ -8,7 +8,9 @@
 //                          passes within ransac_thres of it
 //   finish_hypothesis()    what the best hypothesis returns: nothing (no inlier), its own point, or the DLT over its inliers
 //
-// The second half of the file is KEYPOINT.TRIANGULATION pymvg / naive / refine (et_triangulate_views), built from the same pieces.
+// The second half of the file is KEYPOINT.TRIANGULATION pymvg / naive / refine (et_triangulate_views), built from the same pieces,
+// and its end the gradient of all five methods in the detections (et_triangulate_bwd: backward_joint() replays the DLT that the
+// forward's info word names and differentiates it).
 //
 // The kernel gives every lane one hypothesis and picks the winner with a wave arg-max; the host hook walks them in a loop.  Both
 // take the FIRST hypothesis with the largest count, so they agree.
@@ -171,6 +173,63 @@ ET_TRI_HD void smallest_right_vector(const double (&R)[4][4], double (&X)[3])
     for (int i = 0; i < 3; ++i) X[i] = x[i] / x[3];
 }
 
+// Its sibling for the gradient, by the same route, operation for operation: all four right singular vectors (the columns of
+// Vm), the squares n of their singular values, and the index of the column smallest_right_vector() takes (the FIRST smallest).
+// The two do not share the sweeps as a routine: with them factored out the forward kernels take a third more registers.
+ET_TRI_HD int right_vectors(const double (&R)[4][4], double (&Vm)[4][4], double (&n)[4])
+{
+    double B[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            B[i][k] = k >= i ? R[i][k] : 0.0;
+            Vm[i][k] = i == k ? 1.0 : 0.0;
+        }
+#pragma unroll 1
+    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 4; ++q) {
+                double alpha = 0.0, beta = 0.0, gamma = 0.0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    alpha += B[i][p] * B[i][p];
+                    beta += B[i][q] * B[i][q];
+                    gamma += B[i][p] * B[i][q];
+                }
+                if (fabs(gamma) > 1e-17 * sqrt(alpha * beta)) {
+                    const double zeta = (beta - alpha) / (2.0 * gamma);
+                    const double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const double bp = B[i][p], bq = B[i][q];
+                        B[i][p] = c * bp - s * bq;
+                        B[i][q] = s * bp + c * bq;
+                        const double vp = Vm[i][p], vq = Vm[i][q];
+                        Vm[i][p] = c * vp - s * vq;
+                        Vm[i][q] = s * vp + c * vq;
+                    }
+                }
+            }
+    }
+    int least = 0;
+    double least_n = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        n[k] = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) n[k] += B[i][k] * B[i][k];
+        if (k == 0 || n[k] < least_n) {
+            least_n = n[k];
+            least = k;
+        }
+    }
+    return least;
+}
+
 // image coordinates of joint j in view v
 ET_TRI_HD void detection(const Problem &pr, int f, int v, int j, double &x, double &y)
 {
@@ -192,12 +251,10 @@ ET_TRI_HD void solve_views(const Problem &pr, int f, int j, int mask, double (&X
     smallest_right_vector(R, X);
 }
 
-// Branches 1 and 2: view v with the correspondence the layer found for the feature-map pixel under its detection.  Returns
-// kInfoClamped when that pixel lies outside the map (it is then clamped into it), else 0.
-ET_TRI_HD int solve_single(const Problem &pr, int f, int j, int v, double (&X)[3])
+// The source-view pixel (ox, oy), in image coordinates, that the layer found for the feature-map pixel under the detection
+// (x, y) of view v.  Returns kInfoClamped when that pixel lies outside the map (it is then clamped into it), else 0.
+ET_TRI_HD int correspondence(const Problem &pr, int f, int v, double x, double y, double &ox, double &oy)
 {
-    double x, y;
-    detection(pr, f, v, j, x, y);
     const double qx = (x / pr.resize + 0.5 - pr.ds / 2.0) / pr.ds;
     const double qy = (y / pr.resize + 0.5 - pr.ds / 2.0) / pr.ds;
     int ix, iy, flag = 0;
@@ -213,8 +270,17 @@ ET_TRI_HD int solve_single(const Problem &pr, int f, int j, int v, double (&X)[3
         flag = kInfoClamped;
     }
     const float *c = pr.corr_pos + ((view_row(pr, f, v) * pr.H + iy) * pr.W + ix) * 2;
-    const double ox = ((double)c[0] * pr.ds + pr.ds / 2.0 - 0.5) * pr.resize;
-    const double oy = ((double)c[1] * pr.ds + pr.ds / 2.0 - 0.5) * pr.resize;
+    ox = ((double)c[0] * pr.ds + pr.ds / 2.0 - 0.5) * pr.resize;
+    oy = ((double)c[1] * pr.ds + pr.ds / 2.0 - 0.5) * pr.resize;
+    return flag;
+}
+
+// Branches 1 and 2: view v with its correspondence in the source view.  Returns correspondence()'s flag.
+ET_TRI_HD int solve_single(const Problem &pr, int f, int j, int v, double (&X)[3])
+{
+    double x, y, ox, oy;
+    detection(pr, f, v, j, x, y);
+    const int flag = correspondence(pr, f, v, x, y, ox, oy);
     double R[4][4] = {};
     add_view(R, pr.krt + view_row(pr, f, v) * 12, x, y);
     add_view(R, pr.other_krt + view_row(pr, f, v) * 12, ox, oy);
@@ -443,6 +509,106 @@ inline void views_joint_serial(const ViewsProblem &vp, int f, int j)
         if (hy.count > best.count) best = hy;
     }
     finish_views(vp, f, j, selected, best);
+}
+
+// ---- the gradient of every lifting above in its detections (et_triangulate_bwd) ----------------------------------------------------
+// The info word of the forward names the rows A of the DLT that produced the point: the views of bits 8-15, or -- bits 16-17 set,
+// the epipolar method's single-view branches -- that one view and its correspondence in the source view.  With A fixed at that
+// decision, v the unit right singular vector of the smallest singular value s4 and X = v[:3] / v[3]:
+//   gv = (gX / v3, -(gX . v[:3]) / v3^2)
+//   w  = - sum over the other three right vectors v_k of v_k (v_k . gv) / (s_k^2 - s4^2)      (pinv(A^T A - s4^2 I) applied to gv)
+//   gA = (A w) v^T + (A v) w^T ;  the detection (x, y) of a used view receives gA[row_x] . P[2] and gA[row_y] . P[2]
+// R is rebuilt by the forward's own routines in the forward's order, so v IS the forward's vector.  A vanishing gap s3^2 - s4^2
+// is not guarded: the result is then what float64 autograd through an SVD gives as well (inf or NaN).
+struct BackwardProblem {
+    Problem pr;                // conf, ransac_thres, conf_thres, dlt, out, info unused; other_krt and corr_pos both given or both NULL
+    const int32_t *word;       // (F, J) the forward's info
+    const double *grad_out;    // (F, J, 3)
+    float *grad_pts;           // (F, V, J, 2), every element written
+};
+
+// Writes all 2 V values of the joint: rounded once to float32, exactly 0 for a view that was not used.
+ET_TRI_HD void backward_joint(const BackwardProblem &bp, int f, int j)
+{
+    const Problem &pr = bp.pr;
+    const int word = bp.word[(size_t)f * pr.J + j];
+    const int branch = word >> 16 & 3;
+    int used = word >> 8 & 0xff & ((1 << pr.V) - 1);
+    double R[4][4] = {};
+    bool solved = false;
+    if (branch != 0) {
+        // (branch bits without the two arrays -- a word of the epipolar method handed to the backward of the views -- are not followed)
+        if (used != 0 && pr.other_krt && pr.corr_pos) {
+            int v = 0;
+            while (!(used >> v & 1)) ++v;
+            used = 1 << v;
+            double x, y, ox, oy;
+            detection(pr, f, v, j, x, y);
+            correspondence(pr, f, v, x, y, ox, oy);
+            add_view(R, pr.krt + view_row(pr, f, v) * 12, x, y);
+            add_view(R, pr.other_krt + view_row(pr, f, v) * 12, ox, oy);
+            solved = true;
+        }
+    } else if ((used & (used - 1)) != 0) {             // two views or more
+        for (int v = 0; v < pr.V; ++v)
+            if (used >> v & 1) {
+                double x, y;
+                detection(pr, f, v, j, x, y);
+                add_view(R, pr.krt + view_row(pr, f, v) * 12, x, y);
+            }
+        solved = true;
+    }
+    double vec[4] = {0.0, 0.0, 0.0, 0.0}, w[4] = {0.0, 0.0, 0.0, 0.0};
+    if (solved) {
+        double Vm[4][4], n[4];
+        const int least = right_vectors(R, Vm, n);
+        double n4 = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k == least) {
+                n4 = n[k];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) vec[i] = Vm[i][k];
+            }
+        const double *g = bp.grad_out + ((size_t)f * pr.J + j) * 3;
+        const double gv[4] = {g[0] / vec[3], g[1] / vec[3], g[2] / vec[3],
+                              -(g[0] * vec[0] + g[1] * vec[1] + g[2] * vec[2]) / (vec[3] * vec[3])};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k != least) {
+                double d = 0.0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) d += Vm[i][k] * gv[i];
+                const double c = d / (n[k] - n4);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) w[i] -= Vm[i][k] * c;
+            }
+    }
+    for (int v = 0; v < pr.V; ++v) {
+        float gx = 0.f, gy = 0.f;
+        if (solved && (used >> v & 1)) {
+            const float *P = pr.krt + view_row(pr, f, v) * 12;
+            double x, y;
+            detection(pr, f, v, j, x, y);
+            double aw0 = 0.0, av0 = 0.0, aw1 = 0.0, av1 = 0.0, pw = 0.0, pv = 0.0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const double p2 = (double)P[8 + i];
+                const double r0 = x * p2 - (double)P[i], r1 = y * p2 - (double)P[4 + i];
+                aw0 += r0 * w[i];
+                av0 += r0 * vec[i];
+                aw1 += r1 * w[i];
+                av1 += r1 * vec[i];
+                pw += p2 * w[i];
+                pv += p2 * vec[i];
+            }
+            gx = (float)(aw0 * pv + av0 * pw);
+            gy = (float)(aw1 * pv + av1 * pw);
+        }
+        float *o = bp.grad_pts + (view_row(pr, f, v) * pr.J + j) * 2;
+        o[0] = gx;
+        o[1] = gy;
+    }
 }
 
 #undef ET_TRI_HD

@@ -2,7 +2,7 @@
 // (vision/triangulation.py:234-348).  One wave per (frame, joint), four waves per block, one lane per hypothesis; float64.
 // No atomics, no LDS: the result is bit-reproducible from run to run.  KEYPOINT.TRIANGULATION naive / refine (:99-232) search the
 // same hypotheses without corr_pos and take the same mapping; pymvg (:425-441) has nothing to search, so every LANE takes one
-// (frame, joint).
+// (frame, joint).  So does every lane of the gradient (et_triangulate_bwd): the forward's info word names the DLT to differentiate.
 #include "et_common.h"
 #include "et_triangulate.h"
 
@@ -59,6 +59,38 @@ __global__ __launch_bounds__(kPymvgBlock) void triangulate_pymvg_kernel(const et
     const long long item = (long long)blockIdx.x * kPymvgBlock + threadIdx.x;
     if (item >= (long long)vp.pr.F * vp.pr.J) return;
     et_tri::pymvg_joint(vp, (int)(item / vp.pr.J), (int)(item % vp.pr.J));
+}
+
+// the gradient in the detections: one lane per (frame, joint), as pymvg -- the info word leaves nothing to search
+__global__ __launch_bounds__(kPymvgBlock) void triangulate_bwd_kernel(const et_tri::BackwardProblem bp)
+{
+    const long long item = (long long)blockIdx.x * kPymvgBlock + threadIdx.x;
+    if (item >= (long long)bp.pr.F * bp.pr.J) return;
+    et_tri::backward_joint(bp, (int)(item / bp.pr.J), (int)(item % bp.pr.J));
+}
+
+// The forwards' checks.  other_krt / corr_pos NULL: the backward of et_triangulate_views (H, W, downsample, resize are not read).
+int make_backward_problem(const char *what, int32_t F, int32_t V, int32_t J, int32_t H, int32_t W, const float *pts, const float *krt,
+                          const float *other_krt, const float *corr_pos, float downsample, float resize, const int32_t *info,
+                          const double *grad_out, float *grad_pts, et_tri::BackwardProblem *bp)
+{
+    if (F < 1 || J < 1 || (long long)F * J > 0x7fffffffLL - kWavesPerBlock) return fail("%s: bad sizes F=%d J=%d", what, F, J);
+    if (V < 1 || V > et_tri::kMaxViews) return fail("%s: V=%d outside [1, %d]", what, V, et_tri::kMaxViews);
+    if (!pts || !krt || !info || !grad_out || !grad_pts) return fail("%s: NULL pointer", what);
+    if (!other_krt != !corr_pos) return fail("%s: other_krt and corr_pos must both be given or both be NULL", what);
+    if (corr_pos) {
+        if (H < 1 || W < 1) return fail("%s: bad map size H=%d W=%d", what, H, W);
+        if (!(downsample > 0.f) || !(resize > 0.f)) return fail("%s: downsample / resize must be positive", what);
+    } else {
+        H = W = 0;
+        downsample = resize = 0.f;
+    }
+    bp->pr = et_tri::Problem{F, V, J, H, W, pts, nullptr, krt, other_krt, corr_pos, (double)downsample, (double)resize, 0.0, 0.f, 0,
+                             nullptr, nullptr};
+    bp->word = info;
+    bp->grad_out = grad_out;
+    bp->grad_pts = grad_pts;
+    return 0;
 }
 
 int make_views_problem(const char *what, int32_t F, int32_t V, int32_t J, const float *pts, const float *conf, const float *krt,
@@ -147,6 +179,33 @@ int et_debug_host_triangulate_views(int32_t F, int32_t V, int32_t J, const float
         return e;
     for (int f = 0; f < F; ++f)
         for (int j = 0; j < J; ++j) et_tri::views_joint_serial(vp, f, j);
+    return 0;
+}
+
+int et_triangulate_bwd(int32_t F, int32_t V, int32_t J, int32_t H, int32_t W, const float *pts, const float *krt,
+                       const float *other_krt, const float *corr_pos, float downsample, float resize, const int32_t *info,
+                       const double *grad_out, float *grad_pts, void *stream)
+{
+    et_tri::BackwardProblem bp;
+    if (int e = make_backward_problem("et_triangulate_bwd", F, V, J, H, W, pts, krt, other_krt, corr_pos, downsample, resize, info,
+                                      grad_out, grad_pts, &bp))
+        return e;
+    const long long items = (long long)F * J;
+    hipLaunchKernelGGL(triangulate_bwd_kernel, dim3((unsigned)((items + kPymvgBlock - 1) / kPymvgBlock)), dim3(kPymvgBlock), 0,
+                       (hipStream_t)stream, bp);
+    return check_launch("et_triangulate_bwd");
+}
+
+int et_debug_host_triangulate_bwd(int32_t F, int32_t V, int32_t J, int32_t H, int32_t W, const float *pts, const float *krt,
+                                  const float *other_krt, const float *corr_pos, float downsample, float resize,
+                                  const int32_t *info, const double *grad_out, float *grad_pts)
+{
+    et_tri::BackwardProblem bp;
+    if (int e = make_backward_problem("et_debug_host_triangulate_bwd", F, V, J, H, W, pts, krt, other_krt, corr_pos, downsample,
+                                      resize, info, grad_out, grad_pts, &bp))
+        return e;
+    for (int f = 0; f < F; ++f)
+        for (int j = 0; j < J; ++j) et_tri::backward_joint(bp, f, j);
     return 0;
 }
 

@@ -186,10 +186,15 @@ class MultiViewPoseModel(nn.Module):
                                     projections alone, so all three also work with EPIPOLAR.MULTITEST; rpsm without its dict
                                     is pymvg, and an unknown name is a ValueError.
         Gradient: with EPIPOLAR_AMD.PEAK_GRAD the detections arrive attached to the heat maps (ops.heatmap_peaks(with_grad=True)),
-        and the default route -- the float64 torch DLT of triangulate.py, torch.linalg.svd -- differentiates in them, so a loss on
-        the lifted points reaches the network.  The HIP liftings (ops.triangulate_views, ops.triangulate_epipolar, ops.rpsm)
-        still return no gradient."""
+        and every DLT lifting differentiates in them, so a loss on the lifted points reaches the network: the default route (the
+        float64 torch DLT of triangulate.py, torch.linalg.svd) through torch's autograd, the HIP liftings pymvg / naive / refine
+        (ops.triangulate_views) and epipolar / epipolar_dlt (ops.triangulate_epipolar) through one HIP kernel
+        (et_triangulate_bwd), called with with_grad=True exactly when PEAK_GRAD is set.  It is the gradient of the DLT the
+        forward settled on -- the selected views, the winning pair, the inliers, or the one view with its correspondence -- in
+        the detections that DLT used; the selection, the scores, the projections and corr_pos are constants.  ops.rpsm returns
+        no gradient: a grid search has none."""
         cfg = self.cfg
+        grad = {"with_grad": True} if backbones.peak_grad(cfg) else {}     # (PEAK_GRAD off: exactly the calls without the keyword)
         m, j, _ = batch_locs.shape
         f = m // num_views
         scale = float(cfg.DATASETS.IMAGE_RESIZE) * float(cfg.DATASETS.PREDICT_RESIZE)
@@ -206,7 +211,7 @@ class MultiViewPoseModel(nn.Module):
                 pts.contiguous(), batch_scos.reshape(f, num_views, j).contiguous(), planes(KRT), planes(other_KRT),
                 corr_pos.reshape(f, num_views, *corr_pos.shape[-3:]).contiguous(), downsample=float(cfg.BACKBONE.DOWNSAMPLE),
                 resize=scale, conf_thres=float(getattr(cfg.KEYPOINT, "CONF_THRES", 0.05)),
-                ransac_thres=float(getattr(cfg.KEYPOINT, "RANSAC_THRES", 3)), dlt=method == "epipolar_dlt")
+                ransac_thres=float(getattr(cfg.KEYPOINT, "RANSAC_THRES", 3)), dlt=method == "epipolar_dlt", **grad)
         if method == "rpsm" and rpsm is not None:
             if heatmaps is None:
                 raise ValueError("KEYPOINT.TRIANGULATION rpsm scores the heat maps, and EPIPOLAR.MULTITEST keeps none (every other "
@@ -240,7 +245,7 @@ class MultiViewPoseModel(nn.Module):
                 pts.contiguous(), batch_scos.reshape(f, num_views, j).contiguous(),
                 KRT.to(dev, torch.float32).reshape(f, num_views, 3, 4).contiguous(), method=method,
                 conf_thres=float(getattr(cfg.KEYPOINT, "CONF_THRES", 0.05)),
-                ransac_thres=float(getattr(cfg.KEYPOINT, "RANSAC_THRES", 3)))
+                ransac_thres=float(getattr(cfg.KEYPOINT, "RANSAC_THRES", 3)), **grad)
         return triangulate_dlt(pts, KRT.to(batch_locs.device).view(f, num_views, 3, 4), batch_scos.view(f, num_views, j),
                                conf_thres=float(getattr(cfg.KEYPOINT, "CONF_THRES", 0.05)))
 

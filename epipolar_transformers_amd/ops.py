@@ -850,9 +850,54 @@ def heatmap_peaks(heatmaps: torch.Tensor, radius: float, downsample: float, thre
     return _heatmap_peaks(heatmaps.detach().contiguous(), *args)
 
 
+def _triangulate_bwd(pts, krt, other_krt, corr_pos, downsample: float, resize: float, info, grad_out):
+    """et_triangulate_bwd: the (F,V,J,2) float32 gradient in `pts` of either lifting (other_krt / corr_pos None: the views')."""
+    f, v, j, _ = pts.shape
+    h, w = (0, 0) if corr_pos is None else corr_pos.shape[2:4]
+    grad_out = grad_out.to(torch.float64).contiguous()
+    _require_gpu(grad_out, "grad_out", torch.float64)
+    if tuple(grad_out.shape) != (f, j, 3) or grad_out.device != pts.device:
+        raise ValueError("grad_out must be (%d,%d,3) on %s, got %s on %s" % (f, j, pts.device, tuple(grad_out.shape), grad_out.device))
+    grad = _empty(None, like=pts)
+    _call("et_triangulate_bwd", pts, f, v, j, h, w, _ptr(pts), _ptr(krt), _ptr(other_krt), _ptr(corr_pos), float(downsample),
+          float(resize), _ptr(info), _ptr(grad_out), _ptr(grad), _stream(pts))
+    return grad
+
+
+def _triangulate_epipolar(pts, conf, krt, other_krt, corr_pos, downsample, resize, conf_thres, ransac_thres, dlt, want_info):
+    f, v, j, _ = pts.shape
+    h, w = corr_pos.shape[2:4]
+    out = _empty((f, j, 3), device=pts.device, dtype=torch.float64)
+    info = torch.empty((f, j), dtype=torch.int32, device=pts.device) if want_info else None
+    _call("et_triangulate_epipolar", pts, f, v, j, h, w, _ptr(pts), _ptr(conf), _ptr(krt), _ptr(other_krt), _ptr(corr_pos),
+          downsample, resize, conf_thres, ransac_thres, dlt, _ptr(out), _ptr(info), _stream(pts))
+    return out, info
+
+
+class TriangulateEpipolar(torch.autograd.Function):
+    """et_triangulate_epipolar / et_triangulate_bwd.  Only the detections receive a gradient: the selection by the scores is
+    discrete, and the projections and corr_pos are constants.  The info word is all the backward needs of the forward."""
+
+    @staticmethod
+    def forward(ctx, pts, conf, krt, other_krt, corr_pos, *call):
+        ctx.set_materialize_grads(False)
+        out, info = _triangulate_epipolar(pts, conf, krt, other_krt, corr_pos, *call, True)
+        ctx.save_for_backward(pts, krt, other_krt, corr_pos, info)
+        ctx.call = call[:2]
+        ctx.mark_non_differentiable(info)
+        return out, info
+
+    @staticmethod
+    def backward(ctx, grad_out, _):
+        if grad_out is None:
+            return (None,) * 10
+        pts, krt, other_krt, corr_pos, info = ctx.saved_tensors
+        return (_triangulate_bwd(pts, krt, other_krt, corr_pos, *ctx.call, info, grad_out),) + (None,) * 9
+
+
 def triangulate_epipolar(pts: torch.Tensor, conf: torch.Tensor, krt: torch.Tensor, other_krt: torch.Tensor,
                          corr_pos: torch.Tensor, *, downsample: float, resize: float, conf_thres: float, ransac_thres: float,
-                         dlt: bool = False, want_info: bool = False):
+                         dlt: bool = False, want_info: bool = False, with_grad: bool = False):
     """KEYPOINT.TRIANGULATION epipolar (`dlt` False) / epipolar_dlt (True): triangulate_epipolar of
     vision/triangulation.py:234-348 for all frames and joints in ONE kernel (et_triangulate_epipolar, float64 arithmetic).
     pts (F,V,J,2): image coordinates already multiplied by `resize` = IMAGE_RESIZE * PREDICT_RESIZE; conf (F,V,J); krt,
@@ -863,7 +908,14 @@ def triangulate_epipolar(pts: torch.Tensor, conf: torch.Tensor, krt: torch.Tenso
     Two deviations from the reference.  The pair hypotheses are always enumerated: the reference draws 100 random pairs when
     J >= 10 (triangulation.py:303, 322-340), which for V <= 8 is the same hypothesis set in an order that only decides ties;
     this is its own J < 10 branch, deterministic.  A detection whose feature-map pixel lies outside corr_pos is clamped into
-    the map and flagged (info bit 19); the reference wraps a negative index and raises on a large one.  No gradient."""
+    the map and flagged (info bit 19); the reference wraps a negative index and raises on a large one.
+
+    `with_grad` False (the default): the points are detached.  True, and `pts` requires a gradient: the points are differentiable
+    in `pts` (TriangulateEpipolar: et_triangulate_bwd, one launch, no atomics, the same bits from run to run and in any batch).
+    The backward replays the DLT that the info word names -- the pair, the inliers, the selection, or the one view with its
+    correspondence -- with the decision and the correspondence held constant; views that were not used and joints without a
+    point receive exactly 0.  conf, the projections and corr_pos receive no gradient.  A vanishing gap between the two smallest
+    singular values is not guarded: the gradient is then what float64 autograd through torch.linalg.svd gives as well."""
     _require_gpu(pts, "pts")
     if pts.dim() != 4 or pts.shape[-1] != 2:
         raise ValueError("pts must be (F,V,J,2), got %s" % (tuple(pts.shape),))
@@ -878,19 +930,47 @@ def triangulate_epipolar(pts: torch.Tensor, conf: torch.Tensor, krt: torch.Tenso
         raise ValueError("corr_pos must be (F,V,H,W,2) = (%d,%d,H,W,2), got %s" % (f, v, tuple(corr_pos.shape)))
     h, w = corr_pos.shape[2:4]
     _require_f32(corr_pos, "corr_pos", dev, (f, v, h, w, 2))
-    out = _empty((f, j, 3), device=dev, dtype=torch.float64)
-    info = torch.empty((f, j), dtype=torch.int32, device=dev) if want_info else None
-    _call("et_triangulate_epipolar", pts, f, v, j, h, w, _ptr(pts), _ptr(conf), _ptr(krt), _ptr(other_krt), _ptr(corr_pos),
-          float(downsample), float(resize), float(conf_thres), float(ransac_thres), int(bool(dlt)), _ptr(out), _ptr(info),
-          _stream(pts))
+    call = (float(downsample), float(resize), float(conf_thres), float(ransac_thres), int(bool(dlt)))
+    if with_grad and pts.requires_grad and torch.is_grad_enabled():
+        out, info = TriangulateEpipolar.apply(pts, conf.detach(), krt.detach(), other_krt.detach(), corr_pos.detach(), *call)
+    else:
+        out, info = _triangulate_epipolar(pts, conf, krt, other_krt, corr_pos, *call, want_info)
     return (out, info) if want_info else out
 
 
 VIEW_METHODS = {"pymvg": 0, "naive": 1, "refine": 2}
 
 
+def _triangulate_views(pts, conf, krt, method, conf_thres, ransac_thres, want_info):
+    f, v, j, _ = pts.shape
+    out = _empty((f, j, 3), device=pts.device, dtype=torch.float64)
+    info = torch.empty((f, j), dtype=torch.int32, device=pts.device) if want_info else None
+    _call("et_triangulate_views", pts, f, v, j, _ptr(pts), _ptr(conf), _ptr(krt), method, conf_thres, ransac_thres, _ptr(out),
+          _ptr(info), _stream(pts))
+    return out, info
+
+
+class TriangulateViews(torch.autograd.Function):
+    """et_triangulate_views / et_triangulate_bwd.  Only the detections receive a gradient (TriangulateEpipolar)."""
+
+    @staticmethod
+    def forward(ctx, pts, conf, krt, *call):
+        ctx.set_materialize_grads(False)
+        out, info = _triangulate_views(pts, conf, krt, *call, True)
+        ctx.save_for_backward(pts, krt, info)
+        ctx.mark_non_differentiable(info)
+        return out, info
+
+    @staticmethod
+    def backward(ctx, grad_out, _):
+        if grad_out is None:
+            return (None,) * 6
+        pts, krt, info = ctx.saved_tensors
+        return (_triangulate_bwd(pts, krt, None, None, 0.0, 0.0, info, grad_out),) + (None,) * 5
+
+
 def triangulate_views(pts: torch.Tensor, conf: torch.Tensor, krt: torch.Tensor, *, method: str, conf_thres: float,
-                      ransac_thres: float = 3.0, want_info: bool = False):
+                      ransac_thres: float = 3.0, want_info: bool = False, with_grad: bool = False):
     """KEYPOINT.TRIANGULATION pymvg / naive / refine (vision/triangulation.py:425-441, 99-154, 162-232) for all frames and joints
     in ONE kernel (et_triangulate_views, float64 arithmetic): the liftings that need only detections, scores and projections.
     pts (F,V,J,2): image coordinates; conf (F,V,J); krt (F,V,3,4).  `pymvg`: the DLT over the views above `conf_thres`, the
@@ -903,7 +983,14 @@ def triangulate_views(pts: torch.Tensor, conf: torch.Tensor, krt: torch.Tensor, 
     One deviation from the reference, the one `triangulate_epipolar` states: the pair hypotheses of `naive` / `refine` are always
     enumerated.  The reference draws 100 random ordered pairs per joint; for V <= 8 "all ordered pairs in lexicographic order,
     cyclically" is one sequence those draws can produce, it visits every pair, and its result is the result of the enumeration
-    (tests/golden/make_triangulation_ransac_golden.py runs the reference on exactly that sequence).  No gradient."""
+    (tests/golden/make_triangulation_ransac_golden.py runs the reference on exactly that sequence).
+
+    `with_grad` False (the default): the points are detached.  True, and `pts` requires a gradient: the points are differentiable
+    in `pts` (TriangulateViews: et_triangulate_bwd, one launch, no atomics, the same bits from run to run and in any batch) --
+    the gradient of the DLT over the views the info word names (pymvg's selection, naive's winning pair, refine's inliers), the
+    decision held constant; views that were not used and flagged joints receive exactly 0, conf and krt no gradient.  A
+    vanishing gap between the two smallest singular values is not guarded: the gradient is then what float64 autograd through
+    torch.linalg.svd gives as well."""
     if method not in VIEW_METHODS:
         raise ValueError("method must be one of %s, got %r" % (", ".join(VIEW_METHODS), method))
     _require_gpu(pts, "pts")
@@ -914,10 +1001,11 @@ def triangulate_views(pts: torch.Tensor, conf: torch.Tensor, krt: torch.Tensor, 
     _require_f32(pts, "pts", dev)
     _require_f32(conf, "conf", dev, (f, v, j))
     _require_f32(krt, "krt", dev, (f, v, 3, 4))
-    out = _empty((f, j, 3), device=dev, dtype=torch.float64)
-    info = torch.empty((f, j), dtype=torch.int32, device=dev) if want_info else None
-    _call("et_triangulate_views", pts, f, v, j, _ptr(pts), _ptr(conf), _ptr(krt), VIEW_METHODS[method], float(conf_thres),
-          float(ransac_thres), _ptr(out), _ptr(info), _stream(pts))
+    call = (VIEW_METHODS[method], float(conf_thres), float(ransac_thres))
+    if with_grad and pts.requires_grad and torch.is_grad_enabled():
+        out, info = TriangulateViews.apply(pts, conf.detach(), krt.detach(), *call)
+    else:
+        out, info = _triangulate_views(pts, conf, krt, *call, want_info)
     return (out, info) if want_info else out
 
 

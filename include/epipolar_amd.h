@@ -542,6 +542,38 @@ int et_triangulate_views(int32_t F, int32_t V, int32_t J, const float *pts, cons
 int et_debug_host_triangulate_views(int32_t F, int32_t V, int32_t J, const float *pts, const float *conf, const float *krt,
                                     int32_t method, double conf_thres, double ransac_thres, double *out, int32_t *info);
 
+/* The liftings' backward: the gradient of et_triangulate_views (pymvg, naive, refine) and of et_triangulate_epipolar (epipolar,
+ * epipolar_dlt) in the detections.  One launch, one lane per (frame, joint), float64 arithmetic rounded once to float32 on the
+ * store; no atomics, no workspace: the same bits from run to run and whatever else the batch holds.
+ *   pts, krt, other_krt, corr_pos, downsample, resize : the forward's
+ *   info      : (F, J) int32, the word the forward wrote for these inputs
+ *   grad_out  : (F, J, 3) float64 gradient of the world points
+ *   grad_pts  : (F, V, J, 2) float32, EVERY element written
+ * other_krt and corr_pos both NULL: the backward of et_triangulate_views; H, W, downsample and resize are then not read, and a word
+ * with branch bits gives zeros for its joint.  Both non-NULL: the backward of et_triangulate_epipolar.  One of them NULL is an error.
+ * Nothing is searched and nothing was saved: the word names the DLT that produced the point, and that DLT is replayed.
+ *   (info >> 8 & 0xff) == 0 (zeros written, no inlier, fewer than two views), or one view without branch bits: all 2 V values 0
+ *   (info >> 16 & 3) != 0  : the rows of the one view of bits 8-15 and the two rows of other_krt at the correspondence the forward
+ *                            read from corr_pos (the same pixel arithmetic, the same clamp).  The correspondence is a constant --
+ *                            it is piecewise constant in the detection -- so only that view's detection receives a gradient
+ *   otherwise              : the DLT over the views of bits 8-15 -- pymvg's selection, naive's winning pair, refine's inliers,
+ *                            epipolar's pair or inliers, epipolar_dlt's selection
+ * With the rows A (two per view: x P[2] - P[0], y P[2] - P[1]) fixed at that decision, v the unit right singular vector of the
+ * smallest singular value s4, X = v[:3] / v[3] and gX = grad_out:
+ *   gv = (gX / v3, -(gX . v[:3]) / v3^2) ;  w = - sum_{k<4} v_k (v_k . gv) / (s_k^2 - s4^2) ;  gA = (A w) v^T + (A v) w^T
+ * and the detection (x, y) of a used view receives gA[row_x] . P[2], gA[row_y] . P[2]; a view that was not used receives exactly 0.
+ * The selection is discrete: nothing goes to the scores, and nothing to the projections or corr_pos.  A vanishing gap
+ * s3^2 - s4^2 is NOT guarded: the result is then inf or NaN, as float64 autograd through an SVD gives there.
+ * The argument checks are the forwards' (sizes, V <= 8, NULL pointers, map size, downsample / resize) and come before any launch.
+ * et_debug_host_triangulate_bwd: HOST test hook, no GPU -- the kernel's per-joint routine (csrc/et_triangulate.h) in a serial loop;
+ * host pointers. */
+int et_triangulate_bwd(int32_t F, int32_t V, int32_t J, int32_t H, int32_t W, const float *pts, const float *krt,
+                       const float *other_krt, const float *corr_pos, float downsample, float resize, const int32_t *info,
+                       const double *grad_out, float *grad_pts, void *stream);
+int et_debug_host_triangulate_bwd(int32_t F, int32_t V, int32_t J, int32_t H, int32_t W, const float *pts, const float *krt,
+                                  const float *other_krt, const float *corr_pos, float downsample, float resize,
+                                  const int32_t *info, const double *grad_out, float *grad_pts);
+
 /* KEYPOINT.TRIANGULATION rpsm: the recursive pictorial structure model (modeling/pictorial_cuda.py:222-254) for F frames at once,
  * float32 as the reference.  A first stage scores first_nbins^3 candidate positions per joint (a grid of grid_size around
  * center[f]) against every view's heat map and runs max-product over the limbs of the skeleton; recur_depth levels follow, each
