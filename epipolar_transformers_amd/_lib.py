@@ -25,6 +25,7 @@ ET_VARIANT_WS_BAND = 1048576
 ET_VARIANT_BWD_SPLIT_IN_PLACE = 2097152
 ET_VARIANT_BWD_DETERMINISTIC = 4194304
 ET_ABI_VERSION = 14
+ET_HAS_PAIR_INDEX = 1
 ET_GENERAL_POOLING = 1
 ET_GENERAL_PRIOR_MUL = 2
 ET_GENERAL_COSINE = 4
@@ -69,6 +70,11 @@ _SIGNATURES = {
     "et_epipolar_forward_workspace_error_offset": (ctypes.c_size_t, [_D]),
     "et_epipolar_forward_tiled": (ctypes.c_int, [_D] + [_P] * 12 + [ctypes.c_size_t, _P]),
     "et_epipolar_forward_fused": (ctypes.c_int, [_D] + [_P] * 12 + [ctypes.c_int32, _P, ctypes.c_size_t, _P]),
+    # ET_HAS_PAIR_INDEX: their unindexed siblings' arguments + ref_index, src_index, M_ref, M_src
+    "et_epipolar_forward_tiled_ix": (ctypes.c_int, [_D] + [_P] * 12 + [ctypes.c_size_t, _P] + [_P, _P, ctypes.c_int32, ctypes.c_int32]),
+    "et_epipolar_forward_fused_ix": (ctypes.c_int, [_D] + [_P] * 12 + [ctypes.c_int32, _P, ctypes.c_size_t, _P] +
+                                     [_P, _P, ctypes.c_int32, ctypes.c_int32]),
+    "et_epipolar_backward_tiled_ix": (ctypes.c_int, [_D] + [_P] * 12 + [ctypes.c_size_t, _P] + [_P, _P, ctypes.c_int32, ctypes.c_int32]),
     "et_epipolar_backward_tiled_workspace_bytes": (ctypes.c_size_t, [_D]),
     "et_epipolar_backward_tiled": (ctypes.c_int, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "et_epipolar_backward_tiled_attn": (ctypes.c_int, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),

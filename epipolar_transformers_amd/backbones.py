@@ -188,16 +188,26 @@ class PoseResNet(nn.Module):
         mods += [block(self.inplanes, planes, momentum=self._momentum) for _ in range(1, blocks)]
         return nn.Sequential(*mods)
 
-    def _fuse(self, feat, sampler, other_features, KRT, other_KRT, camera, other_camera):
+    def _fuse(self, feat, sampler, other_features, KRT, other_KRT, camera, other_camera, ref_index=None, src_index=None):
         """getOtherFeat (resnet.py:377-388): epipolar layer + `ret + feat`, with the adds fused into the
-        epilogue kernel when the layer runs in eval mode."""
+        epilogue kernel when the layer runs in eval mode.  `ref_index` / `src_index` (EPIPOLAR_AMD.PAIR_INDEX): `feat` /
+        `other_features` are stacks of maps and pair n -- row n of KRT / other_KRT -- is named by index (Epipolar.forward)."""
         if other_features is None:
             return feat, None, None, None
+        if ref_index is None and src_index is None:
+            if self.cfg.VIS.EPIPOLAR_LINE:
+                ret, corr_pos, depth, sample_locs = sampler(feat, other_features, KRT, other_KRT,
+                                                            camera=camera, other_camera=other_camera)
+                return ret + feat, corr_pos, depth, sample_locs
+            return sampler.forward_fused(feat, other_features, KRT, other_KRT, camera=camera, other_camera=other_camera)
         if self.cfg.VIS.EPIPOLAR_LINE:
-            ret, corr_pos, depth, sample_locs = sampler(feat, other_features, KRT, other_KRT,
-                                                        camera=camera, other_camera=other_camera)
-            return ret + feat, corr_pos, depth, sample_locs
-        return sampler.forward_fused(feat, other_features, KRT, other_KRT, camera=camera, other_camera=other_camera)
+            from . import ops
+
+            ret, corr_pos, depth, sample_locs = sampler(feat, other_features, KRT, other_KRT, camera=camera, other_camera=other_camera,
+                                                        ref_index=ref_index, src_index=src_index)
+            return ret + ops.gather_pairs(feat, ref_index, "ref_index"), corr_pos, depth, sample_locs
+        return sampler.forward_fused(feat, other_features, KRT, other_KRT, camera=camera, other_camera=other_camera,
+                                     ref_index=ref_index, src_index=src_index)
 
     def trunk(self, x):
         """Image -> the pre-fusion feature map of resnet.py:406 (ResNet stages + the three deconvolutions), without
@@ -220,7 +230,10 @@ class PoseResNet(nn.Module):
         return self.deconv_layers(self.layer4(self.layer3(self.layer2(x))))
 
     def forward(self, x, other_inputs=(None, None, None, None, None, None, None)):
-        other_features, other_KRT, other_heatmaps, KRT, camera, other_camera, other_img = other_inputs
+        other_features, other_KRT, other_heatmaps, KRT, camera, other_camera, other_img = other_inputs[:7]
+        # (an eighth entry, beyond the reference's seven: EPIPOLAR_AMD.PAIR_INDEX -- `other_features` is a stack of maps and row n of
+        #  the batch samples map src_index[n] of it, `_fuse`)
+        ix = {"src_index": other_inputs[7]} if len(other_inputs) > 7 and other_inputs[7] is not None else {}
         if x.is_cuda:
             x = x.contiguous(memory_format=torch.channels_last)             # NHWC all the way to the fused kernel
         x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
@@ -229,17 +242,17 @@ class PoseResNet(nn.Module):
         corr_pos = depth = sample_locs = None
         if merge == "early":
             x, corr_pos, depth, sample_locs = self._fuse(x, self.epipolar_sampler, other_features, KRT, other_KRT,
-                                                         camera, other_camera)
+                                                         camera, other_camera, **ix)
         elif merge == "both":
-            x, _, _, _ = self._fuse(x, self.epipolar_sampler, other_features, KRT, other_KRT, camera, other_camera)
+            x, _, _, _ = self._fuse(x, self.epipolar_sampler, other_features, KRT, other_KRT, camera, other_camera, **ix)
         x = self.layer4(self.layer3(self.layer2(x)))
         feature = self.deconv_layers(x)
         if merge == "late":
             x, corr_pos, depth, sample_locs = self._fuse(feature, self.epipolar_sampler, other_features, KRT,
-                                                         other_KRT, camera, other_camera)
+                                                         other_KRT, camera, other_camera, **ix)
         elif merge == "both":
             x, corr_pos, depth, sample_locs = self._fuse(feature, self.epipolar_sampler1, other_features, KRT,
-                                                         other_KRT, camera, other_camera)
+                                                         other_KRT, camera, other_camera, **ix)
         else:
             x = feature
         heatmap = self.final_layer(x)

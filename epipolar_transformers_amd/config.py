@@ -207,6 +207,10 @@ def default_cfg() -> CfgNode:
                                               # DATASETS.H36M.MAPPING, EPEmean_global, JDR and PCK@th (ops.eval_epe / eval_jdr / eval_pck)
     C.EPIPOLAR_AMD.LOSS_KERNELS = False       # True: training takes its loss from the HIP kernels (ops.heatmap_loss) -- KEYPOINT.LOSS joint |
                                               # smoothmse | mse is read, and without `heatmap` the target is made from `points-2d` on the fly
+    C.EPIPOLAR_AMD.PAIR_INDEX = False         # True: forward_views / forward_multitest hand the layer the trunk's ONE stack of maps and
+                                              # name every (reference, source) pair by index into it -- the tile kernels read the
+                                              # maps in place (ET_HAS_PAIR_INDEX) instead of from torch-gathered per-pair copies;
+                                              # same results (ops.pair_index_applies: where the gather remains)
     C.EPIPOLAR_AMD.TRUNK_DTYPE = "fp32"       # arithmetic of the stock trunk (convolutions of `PoseResNet.trunk`): fp32 (the reference's)
                                               # | bf16 | fp16 = torch.autocast around it; the epipolar layer stays fp32 either way
     return C

@@ -1,4 +1,5 @@
-// libepipolar_amd.so: the MFMA tile formulation of the backward (et_epipolar_backward_tiled, _attn, _det and their _ga forms).
+// libepipolar_amd.so: the MFMA tile formulation of the backward (et_epipolar_backward_tiled, _attn, _det and their _ga forms;
+// et_epipolar_backward_tiled_ix: the float form with the pairs named by index -- grad_src is then the source pool's gradient).
 // Kernels: the ordering (kernels_tile_order.inc, through et_tile_host.h) and the tile kernel (kernels_backward_tile.inc over
 // kernels_tile_common.inc, the helpers shared with the forward).
 #include <algorithm>
@@ -30,7 +31,7 @@ DetWorkspace carve_det_workspace(const TileWorkspace &w, size_t pairs, size_t hw
 int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
                         const float *cam, const float *feat_ref, const float *feat_src, const float *attn,
                         const float *grad_out, const float *grad_attn, float *grad_ref, float *grad_src, void *workspace,
-                        size_t workspace_bytes, void *stream);
+                        size_t workspace_bytes, void *stream, const PairIndex &ix = PairIndex());
 }  // namespace
 
 extern "C" {
@@ -90,6 +91,18 @@ int et_epipolar_backward_tiled_ga(const EtLayerDesc *desc, const float *xs, cons
 {
     return backward_tiled_impl(false, desc, xs, ys, steps, cam, feat_ref, feat_src, attn, grad_out, grad_attn, grad_ref, grad_src,
                                workspace, workspace_bytes, stream);
+}
+
+int et_epipolar_backward_tiled_ix(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                                  const float *cam, const float *feat_ref, const float *feat_src, const float *attn,
+                                  const float *grad_out, const float *grad_attn, float *grad_ref, float *grad_src,
+                                  void *workspace, size_t workspace_bytes, void *stream, const int32_t *ref_index,
+                                  const int32_t *src_index, int32_t M_ref, int32_t M_src)
+{
+    PairIndex ix;
+    if (int e = make_pair_index(desc, "et_epipolar_backward_tiled_ix", ref_index, src_index, M_ref, M_src, &ix)) return e;
+    return backward_tiled_impl(false, desc, xs, ys, steps, cam, feat_ref, feat_src, attn, grad_out, grad_attn, grad_ref, grad_src,
+                               workspace, workspace_bytes, stream, ix);
 }
 
 int et_epipolar_backward_tiled(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
@@ -153,7 +166,7 @@ int launch_bwd_tile_list_as(const BwdTileParams &tp, bool det, int dev, hipStrea
 int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
                         const float *cam, const float *feat_ref, const float *feat_src, const float *attn,
                         const float *grad_out, const float *grad_attn, float *grad_ref, float *grad_src, void *workspace,
-                        size_t workspace_bytes, void *stream)
+                        size_t workspace_bytes, void *stream, const PairIndex &ix)
 {
     const char *bad_args = (!xs || !ys || !steps || !cam || !feat_ref || !feat_src || !grad_out || !grad_ref || !grad_src) ? "NULL pointer" : nullptr;
     TileCall c;
@@ -171,6 +184,7 @@ int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, cons
     std::memset(&tp, 0, sizeof(tp));
     BwdParams &p = tp.b;
     p.d = *desc;
+    set_pair_index(p, ix);
     p.xs = xs; p.ys = ys; p.steps = steps; p.cam = cam;
     p.fref = feat_ref; p.fsrc = feat_src; p.gout = grad_out; p.gattn = grad_attn;
     p.gref = grad_ref; p.gsrc = grad_src;
@@ -188,11 +202,13 @@ int backward_tiled_impl(bool det, const EtLayerDesc *desc, const float *xs, cons
     // deterministic form: the clearing blocks zero the int64 accumulator instead (twice the bytes); grad_src is written whole by
     // det_finish_kernel
     const DetWorkspace dw = carve_det_workspace(w, (size_t)desc->N, (size_t)HW);
-    const size_t clear_vec4 = (size_t)desc->N * HW * (desc->C / 4) * (det ? 2 : 1);     // (C == 256)
+    // (an indexed call's grad_src is the source POOL's gradient: M_src maps, every one cleared -- a map no pair names stays 0)
+    const size_t clear_maps = ix.src_index ? (size_t)ix.M_src : (size_t)desc->N;
+    const size_t clear_vec4 = clear_maps * HW * (desc->C / 4) * (det ? 2 : 1);     // (C == 256)
     // (header = true: the ordering clears the workspace's overflow counter, which the merged launch below counts into)
     if (int e = launch_tile_order(desc, xs, ys, cam, feat_ref, feat_src, w, c.tiles_per_pair, true, w.scales, false,
                                   det ? reinterpret_cast<float4 *>(dw.acc) : reinterpret_cast<float4 *>(grad_src), clear_vec4, st,
-                                  "et_epipolar_backward_tiled(order)"))
+                                  "et_epipolar_backward_tiled(order)", ix))
         return e;
     const unsigned vec4_per_pair = (unsigned)HW * (desc->C / 4);
     if (det) {

@@ -103,6 +103,10 @@ struct FwdParams {
     float *res_base;
     int blocks_per_pair;
     int total_blocks;
+    // tile family only (ET_HAS_PAIR_INDEX): fref / fsrc are POOLS of M_ref / M_src maps and pair n reads maps ref_index[n] /
+    // src_index[n] (pair_map below).  NULL: identity -- pair n owns map n, M_* = N.  Every other array stays per pair.
+    const int *ref_index = nullptr, *src_index = nullptr;
+    int M_ref = 0, M_src = 0;
 };
 
 struct BwdParams {
@@ -113,6 +117,10 @@ struct BwdParams {
     float *gref, *gsrc;
     int blocks_per_pair;
     int total_blocks;
+    // tile family only (ET_HAS_PAIR_INDEX), as FwdParams': fref (M_ref maps), fsrc and gsrc (M_src maps) are pools; gref, gout
+    // and the attention stay per pair
+    const int *ref_index = nullptr, *src_index = nullptr;
+    int M_ref = 0, M_src = 0;
     // gather-form backward (workspace given): per-(pixel, source row) coefficient entries
     int cap;            // entry slots per reference pixel (4 * K)
     int *ent_u;         // [N*HW*cap] source pixel index of the entry
@@ -133,6 +141,16 @@ __device__ __forceinline__ int xcd_remap(int b, int nwg)
     const int xcd = b % kXcds;
     const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return base + b / kXcds;
+}
+
+// The map of pair n inside a pool of M maps (ET_HAS_PAIR_INDEX): index[n], read once for the wave (n is wave-uniform at every
+// call site) and clamped into [0, M) -- an index the host did not check gives a wrong answer, never an access outside the pool.
+// A NULL index is the identity: today's per-pair addressing, untouched.
+__device__ __forceinline__ int pair_map(const int *__restrict__ index, int n, int M)
+{
+    if (!index) return n;
+    const int m = __builtin_amdgcn_readfirstlane(index[n]);
+    return min(max(m, 0), M - 1);
 }
 
 __device__ __forceinline__ float lane_bcast(float v, int src_lane)
@@ -378,4 +396,5 @@ int validate(const EtLayerDesc *d)
 __attribute__((visibility("hidden"))) int et_internal_residual_rows_list(const int *perm, const int *tile_list, const int *tile_count,
                                                                          int tiles_per_pair, int HW, long long total_tiles,
                                                                          const float *out, const float *feat, const unsigned *packed,
-                                                                         const float *bias, float *x, hipStream_t st);
+                                                                         const float *bias, float *x, hipStream_t st,
+                                                                         const int *ref_index = nullptr, int M_ref = 0);

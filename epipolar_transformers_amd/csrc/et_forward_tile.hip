@@ -1,4 +1,5 @@
-// libepipolar_amd.so: the MFMA tile formulation of the forward (et_epipolar_forward_tiled, et_epipolar_forward_fused).
+// libepipolar_amd.so: the MFMA tile formulation of the forward (et_epipolar_forward_tiled, et_epipolar_forward_fused, and their
+// *_ix forms: the same implementations with the pairs named by index into pools of maps, PairIndex in et_tile_host.h).
 // Kernels: the ordering (kernels_tile_order.inc, through et_tile_host.h), the persistent warp-specialised kernel
 // (kernels_forward_tile_ws.inc) and the one-block-per-tile kernel (kernels_forward_tile.inc over kernels_tile_common.inc).
 #include "et_common.h"
@@ -23,11 +24,13 @@ extern "C" int et_dev_ws_profile(long long *device_buffer)
 namespace {
 // The parameter block of the one-block-per-tile kernels (its FwdParams are the persistent kernel's too).
 TileParams fwd_tile_params(const EtLayerDesc *desc, const TileCall &c, const float *xs, const float *ys, const float *steps,
-                           const float *cam, const float *feat_ref, const float *feat_src, float *out, float *attn, float *corr_pos)
+                           const float *cam, const float *feat_ref, const float *feat_src, float *out, float *attn, float *corr_pos,
+                           const PairIndex &ix)
 {
     TileParams tp;
     FwdParams &p = tp.f;
     p.d = *desc;
+    set_pair_index(p, ix);
     p.xs = xs; p.ys = ys; p.steps = steps; p.cam = cam;
     p.fref = feat_ref; p.fsrc = feat_src;
     p.out = out; p.attn = attn; p.corr = corr_pos;
@@ -142,6 +145,16 @@ int launch_fwd_tile_list(const TileParams &tp, int rows, int kpl, int dev, hipSt
 }
 }  // namespace
 
+namespace {
+int forward_tiled_impl(const char *who, const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps, const float *cam,
+                       const float *feat_ref, const float *feat_src, float *out, float *attn, float *corr_pos, const float *res_bias,
+                       float *res_base, void *workspace, size_t workspace_bytes, void *stream, const PairIndex &ix);
+int forward_fused_impl(const char *who, const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps, const float *cam,
+                       const float *feat_ref, const float *feat_src, const void *packed_w, const float *bias, float *x, float *attn,
+                       float *corr_pos, float *out_scratch, int32_t want_out, void *workspace, size_t workspace_bytes, void *stream,
+                       const PairIndex &ix);
+}  // namespace
+
 extern "C" {
 
 size_t et_epipolar_forward_workspace_bytes(const EtLayerDesc *desc)
@@ -169,19 +182,64 @@ int et_epipolar_forward_tiled(const EtLayerDesc *desc, const float *xs, const fl
                               float *attn, float *corr_pos, const float *res_bias, float *res_base,
                               void *workspace, size_t workspace_bytes, void *stream)
 {
+    return forward_tiled_impl("et_epipolar_forward_tiled", desc, xs, ys, steps, cam, feat_ref, feat_src, out, attn, corr_pos, res_bias,
+                              res_base, workspace, workspace_bytes, stream, PairIndex());
+}
+
+int et_epipolar_forward_tiled_ix(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                                 const float *cam, const float *feat_ref, const float *feat_src, float *out,
+                                 float *attn, float *corr_pos, const float *res_bias, float *res_base,
+                                 void *workspace, size_t workspace_bytes, void *stream, const int32_t *ref_index,
+                                 const int32_t *src_index, int32_t M_ref, int32_t M_src)
+{
+    PairIndex ix;
+    if (int e = make_pair_index(desc, "et_epipolar_forward_tiled_ix", ref_index, src_index, M_ref, M_src, &ix)) return e;
+    return forward_tiled_impl("et_epipolar_forward_tiled_ix", desc, xs, ys, steps, cam, feat_ref, feat_src, out, attn, corr_pos,
+                              res_bias, res_base, workspace, workspace_bytes, stream, ix);
+}
+
+int et_epipolar_forward_fused(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                              const float *cam, const float *feat_ref, const float *feat_src, const void *packed_w,
+                              const float *bias, float *x, float *attn, float *corr_pos, float *out_scratch,
+                              int32_t want_out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return forward_fused_impl("et_epipolar_forward_fused", desc, xs, ys, steps, cam, feat_ref, feat_src, packed_w, bias, x, attn,
+                              corr_pos, out_scratch, want_out, workspace, workspace_bytes, stream, PairIndex());
+}
+
+int et_epipolar_forward_fused_ix(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                                 const float *cam, const float *feat_ref, const float *feat_src, const void *packed_w,
+                                 const float *bias, float *x, float *attn, float *corr_pos, float *out_scratch,
+                                 int32_t want_out, void *workspace, size_t workspace_bytes, void *stream,
+                                 const int32_t *ref_index, const int32_t *src_index, int32_t M_ref, int32_t M_src)
+{
+    PairIndex ix;
+    if (int e = make_pair_index(desc, "et_epipolar_forward_fused_ix", ref_index, src_index, M_ref, M_src, &ix)) return e;
+    return forward_fused_impl("et_epipolar_forward_fused_ix", desc, xs, ys, steps, cam, feat_ref, feat_src, packed_w, bias, x, attn,
+                              corr_pos, out_scratch, want_out, workspace, workspace_bytes, stream, ix);
+}
+
+}  // extern "C"
+
+namespace {
+// et_epipolar_forward_tiled and its indexed form (a default PairIndex: the identity, pair n owns map n)
+int forward_tiled_impl(const char *who, const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps, const float *cam,
+                       const float *feat_ref, const float *feat_src, float *out, float *attn, float *corr_pos, const float *res_bias,
+                       float *res_base, void *workspace, size_t workspace_bytes, void *stream, const PairIndex &ix)
+{
     const char *bad_args = (!xs || !ys || !steps || !cam || !feat_ref || !feat_src || !out) ? "NULL pointer"
                            : (res_bias && !res_base)                                        ? "res_bias given without res_base"
                                                                                             : nullptr;
     TileCall c;
-    if (int e = begin_tile_call(desc, "et_epipolar_forward_tiled", bad_args, "et_epipolar_forward", nullptr, workspace, workspace_bytes, &c))
+    if (int e = begin_tile_call(desc, who, bad_args, "et_epipolar_forward", nullptr, workspace, workspace_bytes, &c))
         return e;
     hipStream_t st = (hipStream_t)stream;
-    TileParams tp = fwd_tile_params(desc, c, xs, ys, steps, cam, feat_ref, feat_src, out, attn, corr_pos);
+    TileParams tp = fwd_tile_params(desc, c, xs, ys, steps, cam, feat_ref, feat_src, out, attn, corr_pos, ix);
     tp.f.res_bias = res_bias;
     tp.f.res_base = res_base;
     // 1. order every pair's reference pixels by their epipolar line (also clears the overflow counter)
     if (int e = launch_tile_order(desc, xs, ys, cam, feat_ref, feat_src, c.w, c.tiles_per_pair, true, c.w.scales, true, nullptr, 0, st,
-                                  "et_epipolar_forward_tiled(order)"))
+                                  "et_epipolar_forward_tiled(order)", ix))
         return e;
     const int dev = current_device();
     const int kpl = (desc->K + 63) / 64;
@@ -209,10 +267,10 @@ int et_epipolar_forward_tiled(const EtLayerDesc *desc, const float *xs, const fl
 // The layer's eval-mode forward as ONE data kernel: sampling + attention (as et_epipolar_forward_tiled) with
 // x = feat_ref + bias + out . Wf^T -- bn(z(out)) + out + feat with the BN folded into z (epipolar.py:250-253, resnet.py:388;
 // what et_residual_gemm computes from `out` in a second pass) -- as a third GEMM of the persistent kernel.
-int et_epipolar_forward_fused(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
-                              const float *cam, const float *feat_ref, const float *feat_src, const void *packed_w,
-                              const float *bias, float *x, float *attn, float *corr_pos, float *out_scratch,
-                              int32_t want_out, void *workspace, size_t workspace_bytes, void *stream)
+int forward_fused_impl(const char *who, const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps, const float *cam,
+                       const float *feat_ref, const float *feat_src, const void *packed_w, const float *bias, float *x, float *attn,
+                       float *corr_pos, float *out_scratch, int32_t want_out, void *workspace, size_t workspace_bytes, void *stream,
+                       const PairIndex &ix)
 {
     if (int e = validate(desc)) return e;
     if (!xs || !ys || !steps || !cam || !feat_ref || !feat_src || !packed_w || !bias || !x || !out_scratch)
@@ -224,12 +282,12 @@ int et_epipolar_forward_fused(const EtLayerDesc *desc, const float *xs, const fl
                     desc->C, desc->H, desc->W, desc->K, desc->variant);
     // (its own, narrower eligibility and message above: the descriptor and the shape pass begin_tile_call's checks)
     TileCall c;
-    if (int e = begin_tile_call(desc, "et_epipolar_forward_fused", nullptr, "et_epipolar_forward_tiled", nullptr, workspace, workspace_bytes, &c))
+    if (int e = begin_tile_call(desc, who, nullptr, "et_epipolar_forward_tiled", nullptr, workspace, workspace_bytes, &c))
         return e;
     hipStream_t st = (hipStream_t)stream;
-    const TileParams tp = fwd_tile_params(desc, c, xs, ys, steps, cam, feat_ref, feat_src, out_scratch, attn, corr_pos);
+    const TileParams tp = fwd_tile_params(desc, c, xs, ys, steps, cam, feat_ref, feat_src, out_scratch, attn, corr_pos, ix);
     if (int e = launch_tile_order(desc, xs, ys, cam, feat_ref, feat_src, c.w, c.tiles_per_pair, true, c.w.scales, true, nullptr, 0, st,
-                                  "et_epipolar_forward_fused(order)"))
+                                  "et_epipolar_forward_fused(order)", ix))
         return e;
     const int dev = current_device();
     TileWsParams wp = tile_ws_params(tp.f, c);
@@ -248,7 +306,6 @@ int et_epipolar_forward_fused(const EtLayerDesc *desc, const float *xs, const fl
     // their x rows: the residual GEMM kernel over the list, two tiles per block and trip (round 6: the plain-fp32 kernel this replaces
     // took 76 us for the near-rectified rig's 640 left-over tiles -- 256 KB of weight fragments per eight pixel rows; now 24 us)
     return et_internal_residual_rows_list(c.w.perm, c.w.ovf_list, c.w.ovf_count, c.tiles_per_pair, c.HW, c.total, out_scratch, feat_ref,
-                                          reinterpret_cast<const unsigned *>(packed_w), bias, x, st);
+                                          reinterpret_cast<const unsigned *>(packed_w), bias, x, st, ix.ref_index, ix.M_ref);
 }
-
-}  // extern "C"
+}  // namespace

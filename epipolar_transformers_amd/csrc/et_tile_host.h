@@ -88,13 +88,40 @@ TileWorkspace carve_tile_workspace(void *workspace, size_t tiles, size_t pairs, 
     return w;
 }
 
+// The pair table of an indexed call (ET_HAS_PAIR_INDEX): feat_ref / feat_src are pools of M_ref / M_src maps and pair n reads maps
+// ref_index[n] / src_index[n] (device arrays of N int32; NULL: identity, the unindexed exports' call).
+struct PairIndex {
+    const int *ref_index = nullptr, *src_index = nullptr;
+    int M_ref = 0, M_src = 0;
+};
+// The identity table of an unindexed call's N pairs, or the caller's after its checks (a pool of at least one map; a NULL index
+// names map n, so its pool holds exactly N maps).
+int make_pair_index(const EtLayerDesc *desc, const char *who, const int *ref_index, const int *src_index, int M_ref, int M_src,
+                    PairIndex *ix)
+{
+    if (!desc) return fail("desc is NULL");
+    if (M_ref <= 0 || M_src <= 0) return fail("%s: pools of M_ref=%d / M_src=%d maps", who, M_ref, M_src);
+    if (!ref_index && M_ref != desc->N) return fail("%s: ref_index is NULL (identity) but M_ref=%d is not N=%d", who, M_ref, desc->N);
+    if (!src_index && M_src != desc->N) return fail("%s: src_index is NULL (identity) but M_src=%d is not N=%d", who, M_src, desc->N);
+    ix->ref_index = ref_index; ix->src_index = src_index;
+    ix->M_ref = M_ref; ix->M_src = M_src;
+    return 0;
+}
+template <class Params>
+void set_pair_index(Params &p, const PairIndex &ix)
+{
+    p.ref_index = ix.ref_index; p.src_index = ix.src_index;
+    p.M_ref = ix.M_ref; p.M_src = ix.M_src;
+}
+
 // The ordering of a tile call: tile_keys_kernel (segment and sort key of every reference pixel, whole device; clears the
 // header words when `header`), then tile_order_kernel (one block per pair: sort -> perm, the segments in tile order and the
 // tiles' base lines when `ws_tables`, the scale estimates when `scales`; `clear`: extra blocks that zero a buffer beside the
 // sort -- the backward's grad_src).
 int launch_tile_order(const EtLayerDesc *desc, const float *xs, const float *ys, const float *cam, const float *feat_ref,
                       const float *feat_src, const TileWorkspace &w, int tiles_per_pair, bool header, float *scales,
-                      bool ws_tables, float4 *clear, size_t clear_vec4, hipStream_t st, const char *who)
+                      bool ws_tables, float4 *clear, size_t clear_vec4, hipStream_t st, const char *who,
+                      const PairIndex &ix = PairIndex())
 {
     const int HW = desc->H * desc->W;
     const int perm_stride = tiles_per_pair * kTilePix;
@@ -112,7 +139,7 @@ int launch_tile_order(const EtLayerDesc *desc, const float *xs, const float *ys,
     const unsigned clear_blocks = clear ? (unsigned)std::min<size_t>(2048, (clear_vec4 + 8 * 1024 - 1) / (8 * 1024)) : 0u;
     hipLaunchKernelGGL(tile_order_kernel, dim3(desc->N + clear_blocks), dim3(1024), lds_sort, st, *desc, n2, perm_stride, keys,
                        w.segs_pix, w.perm, feat_ref, feat_src, scales, ws_tables ? w.segs : (float4 *)nullptr,
-                       ws_tables ? w.band : (float4 *)nullptr, clear, clear_vec4);
+                       ws_tables ? w.band : (float4 *)nullptr, clear, clear_vec4, ix.ref_index, ix.src_index, ix.M_ref, ix.M_src);
     return check_launch(who);
 }
 

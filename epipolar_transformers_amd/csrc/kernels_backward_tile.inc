@@ -145,10 +145,12 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
 
     const float *cam = p.cam + (size_t)n * ET_CAM_STRIDE;
     const unsigned map_bytes = (unsigned)HW * C * 4u;
-    const __amdgpu_buffer_rsrc_t src = make_rsrc(p.fsrc + (size_t)n * HW * C, map_bytes);
-    const __amdgpu_buffer_rsrc_t ref = make_rsrc(p.fref + (size_t)n * HW * C, map_bytes);
+    // the pair's maps inside the pools (NULL index: map n); grad_src is the source pool's gradient, so several pairs add into one map
+    const int n_ref = pair_map(p.ref_index, n, p.M_ref), n_src = pair_map(p.src_index, n, p.M_src);
+    const __amdgpu_buffer_rsrc_t src = make_rsrc(p.fsrc + (size_t)n_src * HW * C, map_bytes);
+    const __amdgpu_buffer_rsrc_t ref = make_rsrc(p.fref + (size_t)n_ref * HW * C, map_bytes);
     const __amdgpu_buffer_rsrc_t gout = make_rsrc(p.gout + (size_t)n * HW * C, map_bytes);
-    const __amdgpu_buffer_rsrc_t gsrc = make_rsrc(p.gsrc + (size_t)n * HW * C, map_bytes);
+    const __amdgpu_buffer_rsrc_t gsrc = make_rsrc(p.gsrc + (size_t)n_src * HW * C, map_bytes);
     const float neg_inf = -__builtin_huge_valf();
     // DET: the pair's int64 accumulator and 1 / q; a FINITE contribution of 2^48 quanta or more -- impossible under the
     // bound q is made from (kernels_backward_det.inc) -- is reported in the sticky error word and not added
@@ -748,7 +750,7 @@ __device__ __forceinline__ void bwd_tile_body(const BwdTileParams &tp, const int
                 if (lane == 0) s_red[wave] = xm;
                 __syncthreads();
                 const float sa = pow2_scale_capped(fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3])));
-                tile_gemm_out_split<kTileStride, true>(p.fsrc + (size_t)n * HW * C, map_bytes, s_rows, s_D, ucols, wave, lane,
+                tile_gemm_out_split<kTileStride, true>(p.fsrc + (size_t)n_src * HW * C, map_bytes, s_rows, s_D, ucols, wave, lane,
                                                        tp.scales[n * 4 + 2], tp.scales[n * 4 + 3], [&](int m, int chan, f32x2 v) {
                                                            const int pix = s_pix[m];
                                                            if (pix >= 0 && m / gsize == g)

@@ -83,8 +83,8 @@ __device__ __forceinline__ void fwd_tile_body(const TileParams &tp, const int vb
     const int li = lane & 31, lh = lane >> 5;
 
     const float *cam = p.cam + (size_t)n * ET_CAM_STRIDE;
-    const __amdgpu_buffer_rsrc_t src = make_rsrc(p.fsrc + (size_t)n * HW * C, (unsigned)HW * C * 4u);
-    const __amdgpu_buffer_rsrc_t ref = make_rsrc(p.fref + (size_t)n * HW * C, (unsigned)HW * C * 4u);
+    const __amdgpu_buffer_rsrc_t src = make_rsrc(p.fsrc + (size_t)pair_map(p.src_index, n, p.M_src) * HW * C, (unsigned)HW * C * 4u);
+    const __amdgpu_buffer_rsrc_t ref = make_rsrc(p.fref + (size_t)pair_map(p.ref_index, n, p.M_ref) * HW * C, (unsigned)HW * C * 4u);
     const float neg_inf = -__builtin_huge_valf();
     // outputs through raw buffers: 32-bit offsets, and a store whose offset is past the end is dropped, so
     // "lane >= K", "not lane 0/1" and "output not requested" (empty buffer) need no branches
@@ -513,7 +513,7 @@ __device__ __forceinline__ void fwd_tile_body(const TileParams &tp, const int vb
 
         // ================= phase 3: out = B . F2_U on the matrix cores =================
         if (split_out) {
-            tile_gemm_out_split<kTileStride>(p.fsrc + (size_t)n * HW * C, (unsigned)HW * C * 4u, s_rows, s_D, upad, wave, lane,
+            tile_gemm_out_split<kTileStride>(p.fsrc + (size_t)pair_map(p.src_index, n, p.M_src) * HW * C, (unsigned)HW * C * 4u, s_rows, s_D, upad, wave, lane,
                                              tp.scales[n * 4 + 2], tp.scales[n * 4 + 3], [&](int m, int chan, f32x2 v) {
                                                  const int pix = s_pix[m];
                                                  if (pix >= 0 && m / gsize == g)

@@ -326,7 +326,7 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
                 boff[ui] = s_rows[slot * ROWS + min(unit * 16 + (lane >> 2), U - 1)] * kRowBytes + et_g1_loaded_chunk(lane) * 16;
         }
         const int n = valid ? tile_of(j) / tp.tiles_per_pair : 0;
-        const __amdgpu_buffer_rsrc_t src = make_rsrc(p.fsrc + (size_t)n * HW * C, map_bytes);
+        const __amdgpu_buffer_rsrc_t src = make_rsrc(p.fsrc + (size_t)pair_map(p.src_index, n, p.M_src) * HW * C, map_bytes);
 #pragma unroll
         for (int ks = 0; ks < kD1; ++ks)
 #pragma unroll
@@ -338,7 +338,7 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
         const int U = s_U[slot];
         if (U <= 0) return;
         const int n = tile_of(j) / tp.tiles_per_pair;
-        const __amdgpu_buffer_rsrc_t src = make_rsrc(p.fsrc + (size_t)n * HW * C, map_bytes);
+        const __amdgpu_buffer_rsrc_t src = make_rsrc(p.fsrc + (size_t)pair_map(p.src_index, n, p.M_src) * HW * C, map_bytes);
         const float s_src = tp.scales[n * 4 + 2];
         const float inv = tp.scales[n * 4 + 3];          // 1 / s_src; the A rows carry their own scales (s_ainv)
         const int nunits = (U + 15) >> 4;                // 16-row units of the tile
@@ -471,7 +471,7 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
     const int cfirst = (wave - kWsMatrixWaves) * kCopyPix;    // first pixel of this (vector) wave
     auto copy_load = [&](int jc, bool valid) {
         const int tl = valid ? tile_of(jc) : 0;
-        const __amdgpu_buffer_rsrc_t ref = make_rsrc(p.fref + (size_t)(tl / tp.tiles_per_pair) * HW * C, valid ? map_bytes : 0u);
+        const __amdgpu_buffer_rsrc_t ref = make_rsrc(p.fref + (size_t)pair_map(p.ref_index, tl / tp.tiles_per_pair, p.M_ref) * HW * C, valid ? map_bytes : 0u);
 #pragma unroll
         for (int ii = 0; ii < kCopyPix; ++ii) {
             cpx[ii] = valid ? perm_c[(size_t)tl * kTilePix + cfirst + ii] : -1;
@@ -539,7 +539,7 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
     auto g2_prefetch = [&](int j, bool valid) {
         const int slot = valid ? j % kWsSlots : 0;
         const int n = valid ? tile_of(j) / tp.tiles_per_pair : 0;
-        const float *srcp = p.fsrc + (size_t)n * HW * C;
+        const float *srcp = p.fsrc + (size_t)pair_map(p.src_index, n, p.M_src) * HW * C;
         const int voff = (wave * 64 + 4 * (lane & 15)) * 4;
         const int *rows = s_rows + slot * ROWS;
         const int nks = valid ? (s_U[slot] + 15) >> 4 : 0;      // (U = -1, an overflow tile: 0)
@@ -561,7 +561,7 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
         const int half = half_of(j);
         if (KH == 2 && __builtin_amdgcn_readfirstlane(s_dead[seq_of(j) & 3]) != 0) return;   // (the tile went to the list kernels)
         const int n = tile_of(j) / tp.tiles_per_pair;
-        const float *srcp = p.fsrc + (size_t)n * HW * C;
+        const float *srcp = p.fsrc + (size_t)pair_map(p.src_index, n, p.M_src) * HW * C;
         const float s_src = tp.scales[n * 4 + 2];
         const float inv = tp.scales[n * 4 + 3] * (1.f / 1024.f);
         const float *s_D = s_arr + (j & 1) * kArr;
@@ -706,7 +706,7 @@ __global__ __launch_bounds__((kWsMatrixWaves + NV) * kWave) void epipolar_fwd_ti
             }
             __builtin_amdgcn_sched_barrier(0);      // (G2's accumulators are dead from here: nothing of G3 is hoisted above)
             // the feat rows and the bias of this wave's outputs: accumulator nb, register r  <->  row m(r), channel c0 + 32 nb + li
-            const __amdgpu_buffer_rsrc_t refb = make_rsrc(p.fref + (size_t)n * HW * C, map_bytes);
+            const __amdgpu_buffer_rsrc_t refb = make_rsrc(p.fref + (size_t)pair_map(p.ref_index, n, p.M_ref) * HW * C, map_bytes);
             float fr[2][16];
             auto xoff_of = [&](int r) {      // (re-read from LDS where it is needed: sixteen offsets would cost sixteen registers)
                 const int m = (r & 3) + 8 * (r >> 2) + 4 * lh3;

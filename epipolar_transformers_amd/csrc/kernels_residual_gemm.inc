@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256, 2) void residual_gemm_kernel(const float *__re
                                                                const int *__restrict__ perm = nullptr,
                                                                const int *__restrict__ tile_list = nullptr,
                                                                const int *__restrict__ tile_count = nullptr, int tiles_per_pair = 0,
-                                                               int HW = 0)
+                                                               int HW = 0, const int *__restrict__ ref_index = nullptr, int M_ref = 0)
 {
     static_assert(!LIST || (!STATS && !DY), "the list form is the plain epilogue");
     extern __shared__ char s_rg[];
@@ -133,7 +133,9 @@ __global__ __launch_bounds__(256, 2) void residual_gemm_kernel(const float *__re
     const unsigned nrows = LIST ? (unsigned)kRgRows : (unsigned)min((long long)kRgRows, rows - row0);
     const unsigned span = LIST ? (unsigned)HW * 1024u : nrows * 1024u;
     const __amdgpu_buffer_rsrc_t r_out = make_rsrc(out + row0 * 256, span);
-    const __amdgpu_buffer_rsrc_t r_feat = make_rsrc(HAS_FEAT ? feat + row0 * 256 : out, HAS_FEAT ? span : 0u);
+    // (LIST: `feat` may be a pool of M_ref maps, the tile's pair reading map ref_index[pair]: pair_map, et_common.h)
+    const long long feat_row0 = LIST ? (long long)pair_map(ref_index, max(list_tile, 0) / tiles_per_pair, M_ref) * HW : row0;
+    const __amdgpu_buffer_rsrc_t r_feat = make_rsrc(HAS_FEAT ? feat + feat_row0 * 256 : out, HAS_FEAT ? span : 0u);
     const __amdgpu_buffer_rsrc_t r_x = make_rsrc(x + row0 * 256, span);
     const __amdgpu_buffer_rsrc_t r_w = make_rsrc(packed, (unsigned)kRgPackedWords * 4u);
     const float inv_w = reinterpret_cast<const float *>(packed)[kRgPackedWords];

@@ -113,7 +113,9 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const EtLayerDesc d, i
                                                           float *__restrict__ scales = nullptr,
                                                           float4 *__restrict__ segs = nullptr,
                                                           float4 *__restrict__ band = nullptr,
-                                                          float4 *__restrict__ clear = nullptr, size_t clear_vec4 = 0)
+                                                          float4 *__restrict__ clear = nullptr, size_t clear_vec4 = 0,
+                                                          const int *__restrict__ ref_index = nullptr,
+                                                          const int *__restrict__ src_index = nullptr, int M_ref = 0, int M_src = 0)
 {
     extern __shared__ unsigned long long s_key[];
     // Blocks beyond the pairs (the backward's launch): clear `clear` (grad_src, which the tile kernel adds into) BESIDE the
@@ -136,7 +138,9 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const EtLayerDesc d, i
     if (scales) {
         const int pstep = max(1, HW / 64);
         for (int which = 0; which < 2; ++which) {
-            const float4 *map = reinterpret_cast<const float4 *>((which ? fsrc : fref) + (size_t)n * HW * d.C);
+            // (pair n's maps inside the pools: pair_map, et_common.h)
+            const int nm = which ? pair_map(src_index, n, M_src) : pair_map(ref_index, n, M_ref);
+            const float4 *map = reinterpret_cast<const float4 *>((which ? fsrc : fref) + (size_t)nm * HW * d.C);
             for (int k = wave; k < 64; k += 16) {
                 const int pix = min(k * pstep, HW - 1);
                 const float4 v = map[(size_t)pix * (d.C >> 2) + (lane % (d.C >> 2))];

@@ -440,10 +440,19 @@ class Epipolar(nn.Module):
             host = None
         return self._cams.get(P1, P2, device, host=host)
 
-    def attend(self, feat1, feat2, P1, P2):
-        """The fused kernel only: (out, attn, corr_pos), `out` before the z branch."""
+    def attend(self, feat1, feat2, P1, P2, ref_index=None, src_index=None):
+        """The fused kernel only: (out, attn, corr_pos), `out` before the z branch.  With `ref_index` / `src_index` (host
+        indices, one per pair = per row of P1 / P2; each optional) feat1 / feat2 are stacks of maps the pairs are named from
+        (ops.EpipolarAttendIndexed: no gathered copies, neither made nor saved for the backward)."""
         cam = self._cam(P1, P2, feat1.device)
-        return ops.EpipolarAttend.apply(feat1, feat2, cam, self.layer_spec(), self._attn_grad())
+        if ref_index is None and src_index is None:
+            return ops.EpipolarAttend.apply(feat1, feat2, cam, self.layer_spec(), self._attn_grad())
+        return ops.EpipolarAttendIndexed.apply(feat1, feat2, cam, self.layer_spec(), ref_index, src_index, self._attn_grad())
+
+    @staticmethod
+    def _index_kw(ref_index, src_index) -> dict:
+        """The index arguments of `attend`, only where one is given (a call without them is the call it always was)."""
+        return {} if ref_index is None and src_index is None else dict(ref_index=ref_index, src_index=src_index)
 
     def _attn_grad(self) -> bool:
         """EPIPOLAR_AMD.ATTN_GRAD: the returned attention (`depth`) is a differentiable output of the HIP attend functions, as it
@@ -523,17 +532,24 @@ class Epipolar(nn.Module):
                 finalout = finalout + out                                    # epipolar.py:253
         return finalout, (finalout + feat1 if feat1 is not None else None)  # resnet.py:388
 
-    def forward(self, feat1, feat2, P1, P2, depth=None, camera=None, other_camera=None, ref1=None, ref2=None):
+    def forward(self, feat1, feat2, P1, P2, depth=None, camera=None, other_camera=None, ref1=None, ref2=None,
+                ref_index=None, src_index=None):
         """Same contract as the reference (epipolar.py:82-269):
         feat1, feat2: N x C x H x W ; P1, P2: N x 3 x 4
-        returns (finalout, corr_pos[N,H,W,2], depth[N,K,H,W], sample_locs | None)."""
+        returns (finalout, corr_pos[N,H,W,2], depth[N,K,H,W], sample_locs | None).
+        `ref_index` / `src_index` (beyond the reference): feat1 / feat2 are stacks of M maps and pair n -- row n of P1 / P2 --
+        is (feat1[ref_index[n]], feat2[src_index[n]]); the headline mode reads them in place (`attend`), every other mode
+        gathers them first."""
         self._check_mode(depth, ref1, ref2)
+        if (ref_index is not None or src_index is not None) and (depth is not None or not self._fused_mode(ref1, ref2)):
+            feat1, feat2 = ops.gather_pairs(feat1, ref_index, "ref_index"), ops.gather_pairs(feat2, src_index, "src_index")
+            ref_index = src_index = None
         if depth is not None:
             out, attn, corr_pos = self._attend_with_depth(feat1, feat2, P1, P2, depth)
             return self._result(out, corr_pos, attn, P1, P2, feat2.device)
         fused = self._fused_mode(ref1, ref2)
         if fused:
-            out, attn, corr_pos = self.attend(feat1, feat2, P1, P2)
+            out, attn, corr_pos = self.attend(feat1, feat2, P1, P2, **self._index_kw(ref_index, src_index))
         else:
             out, attn, corr_pos = self._attend_general(feat1, feat2, P1, P2, camera, other_camera, ref1, ref2)
         if fused and self._eval_fast_path((feat1, feat2)) and "z" in self.cfg.EPIPOLAR.PARAMETERIZED:
@@ -560,22 +576,41 @@ class Epipolar(nn.Module):
             return (finalout, corr_pos, attn, locs) + self._debug_geometry(cam)
         return finalout, corr_pos, attn, locs.transpose(0, 1)
 
-    def forward_fused(self, feat1, feat2, P1, P2, camera=None, other_camera=None):
+    def forward_fused(self, feat1, feat2, P1, P2, camera=None, other_camera=None, ref_index=None, src_index=None):
         """forward + `ret + feat` (resnet.py:388).  In eval mode the whole epilogue is ONE GEMM, x = feat + bf + out @ Wf^T:
         for the 256-channel head on maps up to 96 x 96 (K <= 64) a third GEMM INSIDE the persistent forward kernel
         (`ops.forward_fused_nhwc`: `out` never goes through HBM), for the other 256-channel shapes `ops.residual_gemm` behind
         the forward; other widths: the fused kernel emits feat + bf and a library GEMM accumulates into it.
-        Returns (x, corr_pos, depth, None)."""
+        Returns (x, corr_pos, depth, None).  `ref_index` / `src_index`: as `forward`'s; the one-kernel layer and the tile
+        kernels read the stacks in place, the `+ feat` of the other routes takes gathered reference maps."""
         self._check_mode(None, None, None)
+        indexed = ref_index is not None or src_index is not None
+        if indexed and not (self._fused_mode() and "z" in self.cfg.EPIPOLAR.PARAMETERIZED and
+                            ops.pair_index_applies(self.layer_spec(), feat1.shape[1], "forward")):
+            # (what the indexed kernels do not take: today's route on gathered maps)
+            feat1, feat2 = ops.gather_pairs(feat1, ref_index, "ref_index"), ops.gather_pairs(feat2, src_index, "src_index")
+            ref_index = src_index = None
+            indexed = False
         if not self._fused_mode():
             fin, corr_pos, attn, _ = self.forward(feat1, feat2, P1, P2, camera=camera, other_camera=other_camera)
             return fin + feat1, corr_pos, attn, None                         # resnet.py:388
         if not self._eval_fast_path((feat1, feat2)):
-            out, attn, corr_pos = self.attend(feat1, feat2, P1, P2)
-            _, x = self._epilogue_torch(out, feat1)
+            out, attn, corr_pos = self.attend(feat1, feat2, P1, P2, **self._index_kw(ref_index, src_index))
+            _, x = self._epilogue_torch(out, ops.gather_pairs(feat1, ref_index, "ref_index"))
             return x, corr_pos, attn, None
         cam = self._cam(P1, P2, feat1.device)
-        ref, src = ops.to_nhwc(feat1), ops.to_nhwc(feat2)
+        ref = ops.to_nhwc(feat1)
+        src = ref if feat2 is feat1 else ops.to_nhwc(feat2)
+        if indexed:
+            # (C == 256 with the z branch: the one-kernel layer, or the tile forward + the residual GEMM on gathered reference rows)
+            packed, bf = self._packed_z()
+            spec = self.layer_spec()
+            if bool(amd_knob(self.cfg, "FUSED_GEMM3", True)) and ops.pair_index_applies(spec, 256, "fused"):
+                x, attn, corr_pos = ops.forward_fused_nhwc(spec, ref, src, cam, packed, bf, ref_index=ref_index, src_index=src_index)
+            else:
+                out, attn, corr_pos = ops.forward_nhwc(spec, ref, src, cam, ref_index=ref_index, src_index=src_index)
+                x = ops.residual_gemm(out, packed, bf, ops.gather_pairs(ref, ref_index, "ref_index"))
+            return x.permute(0, 3, 1, 2), corr_pos, attn, None
         if "z" in self.cfg.EPIPOLAR.PARAMETERIZED and ref.shape[-1] == 256:
             # x = feat + bf + out . Wf^T in ONE kernel behind the fused forward (no res_base round trip through HBM)
             packed, bf = self._packed_z()

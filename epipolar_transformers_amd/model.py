@@ -89,15 +89,22 @@ class MultiViewPoseModel(nn.Module):
         every row.  Returns the backbone's 8-tuple (resnet.py:437) with the trunk run once per view."""
         net = self.reference
         other_KRT = KRT[source_index.to(KRT.device)]            # KRT on the host: pass a host index to avoid a sync
+        from .config import amd_knob
+
+        by_index = bool(amd_knob(self.cfg, "PAIR_INDEX", False))
         if self.cfg.EPIPOLAR.MERGE != "late" or self.backbone is not self.reference:
             with torch.set_grad_enabled(torch.is_grad_enabled() and bool(self.cfg.EPIPOLAR.OTHER_GRAD)):
                 feats = self.backbone(img)[0]                               # model.py:241-244
+            if by_index and self.cfg.EPIPOLAR.MERGE == "late":
+                # (the source stack as it is + the index: the layer reads map source_index[n] for row n, no gathered copy)
+                return net(img, [feats, other_KRT, None, KRT, camera, other_camera, None, source_index])
             return net(img, [feats[source_index], other_KRT, None, KRT, camera, other_camera, None])
         feature = net.trunk(img)                                            # once per view
-        other = feature[source_index]
+        # (PAIR_INDEX: the layer names its source maps by index into the trunk's stack -- no gathered copy, made or saved for the backward)
+        other, ix = (feature, {"src_index": source_index}) if by_index else (feature[source_index], {})
         if not self.cfg.EPIPOLAR.OTHER_GRAD:
             other = other.detach()
-        x, corr_pos, depth, sample_locs = net._fuse(feature, net.epipolar_sampler, other, KRT, other_KRT, camera, other_camera)
+        x, corr_pos, depth, sample_locs = net._fuse(feature, net.epipolar_sampler, other, KRT, other_KRT, camera, other_camera, **ix)
         heatmap = net.final_layer(x)
         locs, scos = backbones.find_peaks(heatmap, self.cfg.KEYPOINT.SIGMA, self.cfg.BACKBONE.DOWNSAMPLE, grad=backbones.peak_grad(self.cfg))
         return feature, [heatmap], locs, scos, corr_pos, depth, sample_locs, None
@@ -137,11 +144,29 @@ class MultiViewPoseModel(nn.Module):
         (reference, source) pairs."""
         net = self.reference
         m = img.shape[0]
-        frames = m // num_views
         feature = net.trunk(img)
         # the source features come from `self.backbone` (model.py:219): the same network only with SHARE_WEIGHTS
         source = feature if self.backbone is net else self.backbone(img)[0]
-        base = torch.arange(m, device=img.device).view(frames, num_views)
+        x = self._multitest_layer(feature, source, KRT, num_views)
+        heat = net.final_layer(x)
+        locs, scos = backbones.find_peaks(heat, self.cfg.KEYPOINT.SIGMA, self.cfg.BACKBONE.DOWNSAMPLE)
+        locs = locs.view(num_views - 1, m, -1, 2)
+        scos = scos.view(num_views - 1, m, -1)
+        best, which = scos.max(0)                                           # model.py:233-236
+        locs = torch.gather(locs, 0, which[None, ..., None].expand(-1, -1, -1, 2)).squeeze(0)
+        return locs, best
+
+    def _multitest_layer(self, feature, source, KRT, num_views: int):
+        """forward_multitest's layer call: x (F*V*(V-1), C, H, W) of every (reference, source) pair, shift-major, from the
+        stacks `feature` / `source` (F*V maps each, frame-major).  With EPIPOLAR_AMD.PAIR_INDEX the pairs are named by index
+        into the two stacks; otherwise both operands are gathered first (2 x F*V*(V-1) maps)."""
+        from .config import amd_knob
+
+        net = self.reference
+        m = feature.shape[0]
+        frames = m // num_views
+        by_index = bool(amd_knob(self.cfg, "PAIR_INDEX", False))
+        base = torch.arange(m, device="cpu" if by_index else feature.device).view(frames, num_views)
         ref_idx, src_idx = [], []
         for shift in range(1, num_views):
             ref_idx.append(base.reshape(-1))
@@ -156,15 +181,11 @@ class MultiViewPoseModel(nn.Module):
             assert len(ids) >= num_views, "EPIPOLAR.PRIOR needs DATASETS.CAMERAS to name every view"
             camera = [ids[int(i) % num_views] for i in ref_idx.tolist()]
             other_camera = [ids[int(i) % num_views] for i in src_idx.tolist()]
-        x, _, _, _ = net._fuse(feature[ref_idx], net.epipolar_sampler, source[src_idx], Kc[ref_idx.cpu()], Kc[src_idx.cpu()],
-                               camera, other_camera)
-        heat = net.final_layer(x)
-        locs, scos = backbones.find_peaks(heat, self.cfg.KEYPOINT.SIGMA, self.cfg.BACKBONE.DOWNSAMPLE)
-        locs = locs.view(num_views - 1, m, -1, 2)
-        scos = scos.view(num_views - 1, m, -1)
-        best, which = scos.max(0)                                           # model.py:233-236
-        locs = torch.gather(locs, 0, which[None, ..., None].expand(-1, -1, -1, 2)).squeeze(0)
-        return locs, best
+        if by_index:
+            return net._fuse(feature, net.epipolar_sampler, source, Kc[ref_idx], Kc[src_idx], camera, other_camera,
+                             ref_index=ref_idx, src_index=src_idx)[0]
+        return net._fuse(feature[ref_idx], net.epipolar_sampler, source[src_idx], Kc[ref_idx.cpu()], Kc[src_idx.cpu()],
+                         camera, other_camera)[0]
 
     # ------------------------------------------------------------------------------------------ N3
     def lift(self, batch_locs: torch.Tensor, batch_scos: torch.Tensor, KRT: torch.Tensor, num_views: int,

@@ -301,34 +301,171 @@ _TILE_BITS = (_lib.ET_VARIANT_TILE_SPLIT | _lib.ET_VARIANT_TILE_CLASSIC |
               _lib.ET_VARIANT_WS_SETPRIO | _lib.ET_VARIANT_TILE_EXACT | _lib.ET_VARIANT_WS_BAND | _lib.ET_VARIANT_BWD_SPLIT_IN_PLACE)   # bits that tune the tile path instead of leaving it
 
 
-def _require_pair(spec: LayerSpec, ref, src, cam, c: int = None):
+def _require_pair(spec: LayerSpec, ref, src, cam, c: int = None, ref_index=None, src_index=None):
     """feat_ref / feat_src / cam of the headline entry points: contiguous (N,H,W,C) maps of the layer's size (with `c` channels,
-    where the kernel is written for one width) and their (N,27) algebra, on one GPU.  Returns (n, h, w, c)."""
+    where the kernel is written for one width) and their (N,27) algebra, on one GPU.  With an index (the device copy
+    _pair_indices returns) that operand is a POOL of any number of maps and N is the number of cameras.  Returns (n, h, w, c)."""
     for t, nm in ((ref, "feat_ref"), (src, "feat_src")):
         _require_f32(t, nm, ref.device, msg="feat_ref / feat_src must be contiguous (N,H,W,C) tensors")
-    n, h, w, ch = ref.shape
-    if (h, w) != (spec.H, spec.W) or src.shape != ref.shape or (c is not None and ch != c):
-        raise ValueError("feature maps %s / %s do not match the layer's %dx%d%s" %
-                         (tuple(ref.shape), tuple(src.shape), spec.H, spec.W, "" if c is None else " x %d" % c))
+    indexed = ref_index is not None or src_index is not None
+    if ref.dim() != 4 or src.dim() != 4:
+        raise ValueError("feat_ref / feat_src must be contiguous (N,H,W,C) tensors")
+    n, (_, h, w, ch) = (cam.shape[0] if indexed else ref.shape[0]), ref.shape
+    if ((h, w) != (spec.H, spec.W) or src.shape[1:] != ref.shape[1:] or (c is not None and ch != c) or
+            (ref_index is None and ref.shape[0] != n) or (src_index is None and src.shape[0] != n)):
+        raise ValueError("feature maps %s / %s do not match the layer's %dx%d%s%s" %
+                         (tuple(ref.shape), tuple(src.shape), spec.H, spec.W, "" if c is None else " x %d" % c,
+                          " (%d pairs; an operand without an index holds one map per pair)" % n if indexed else ""))
     _require_cam(cam, n, ref.device)
     return n, h, w, ch
 
 
+# ---- pairs named by index into a stack of maps (ET_HAS_PAIR_INDEX) -----------------------------------------------------------
+# The *_ix entry points read pair n's maps as feat_ref[ref_index[n]] / feat_src[src_index[n]] from two POOLS (they may be one
+# tensor) instead of from private per-pair copies.  forward_nhwc / forward_fused_nhwc / backward_nhwc take the indices as CPU
+# integer tensors or sequences: checked on the HOST (length N, integer dtype, range: ValueError), uploaded once and cached by
+# value.  Where the indexed kernels do not apply (pair_index_applies), or the index is a CUDA tensor (its values are not on the
+# host: checking them would synchronise), the same call gathers the pairs' maps with torch and runs the unindexed kernels.
+PAIR_INDEX_FORMS = ("forward", "fused", "tile", "tile_det", "gather", "atomic", "pixel", "general")
+
+
+def pair_index_applies(spec: LayerSpec, c: int, form: str) -> bool:
+    """True when a call of `form` on `c` channels runs the indexed tile kernels; False = the gathered route (same results).
+    `form`: "forward" (forward_nhwc), "fused" (forward_fused_nhwc), a backward form of backward_nhwc ("tile": indexed;
+    "tile_det", "gather", "atomic": not), "pixel" (the per-pixel forward) or "general" (a mode of the general kernels).
+    False for C != 256, a deterministic spec (ET_VARIANT_BWD_DETERMINISTIC), a variant bit that selects the per-pixel kernels,
+    and any shape the tile path does not take."""
+    if form not in PAIR_INDEX_FORMS:
+        raise ValueError("unknown form %r (one of %s)" % (form, ", ".join(PAIR_INDEX_FORMS)))
+    if c != 256 or form not in ("forward", "fused", "tile"):
+        return False
+    if spec.variant & _lib.ET_VARIANT_BWD_DETERMINISTIC:
+        return False
+    if form == "tile" and (spec.variant & _BWD_EXPLICIT):
+        return False
+    if form != "tile" and (spec.variant & ~_TILE_BITS) != 0:
+        return False
+    if form == "fused":
+        return fused_layer_applies(spec, c)
+    d = spec.desc(1, c)
+    return int(_lib.load().et_epipolar_forward_workspace_bytes(ctypes.byref(d))) > 0
+
+
+def check_pair_index(index, name: str, n: int, m: int) -> np.ndarray:
+    """`index` (a CPU integer tensor or a sequence of ints) as a contiguous int32 array, after the checks the kernels rely on:
+    one dimension of length `n`, an integer dtype, every value in [0, m).  Host work only; raises ValueError."""
+    if torch.is_tensor(index):
+        if index.is_cuda:
+            raise ValueError("%s is a CUDA tensor: its values cannot be checked without a synchronisation" % name)
+        if index.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise ValueError("%s must have an integer dtype, got %s" % (name, index.dtype))
+        arr = index.detach().numpy()
+    else:
+        arr = np.asarray(index)
+        if arr.size and arr.dtype.kind not in "iu":
+            raise ValueError("%s must hold integers, got dtype %s" % (name, arr.dtype))
+    if arr.ndim != 1 or arr.shape[0] != n:
+        raise ValueError("%s must name one map per pair: length %d, got shape %s" % (name, n, tuple(arr.shape)))
+    if n and (int(arr.min()) < 0 or int(arr.max()) >= m):
+        raise ValueError("%s has values in [%d, %d]: outside the pool's %d maps" % (name, int(arr.min()), int(arr.max()), m))
+    return np.ascontiguousarray(arr, dtype=np.int32)
+
+
+class PairIndexCache:
+    """Device copies of pair tables, keyed by VALUE (the bytes of the int32 array and the device) like camera.PairAlgebraCache:
+    a model hands the same table every step, a recycled host address with other values must not hit."""
+
+    def __init__(self, max_entries: int = 16):
+        self.max_entries = max_entries
+        self._store = {}
+        self._lock = threading.Lock()
+
+    def get(self, arr: np.ndarray, device) -> torch.Tensor:
+        key = (arr.tobytes(), str(device))
+        with self._lock:
+            hit = self._store.get(key)
+            if hit is None:
+                hit = torch.from_numpy(arr.copy()).pin_memory().to(device, non_blocking=True)
+                if len(self._store) >= self.max_entries:
+                    self._store.pop(next(iter(self._store)))
+                self._store[key] = hit
+        return hit
+
+
+_pair_index_cache = PairIndexCache()
+
+
+def _is_device_index(index) -> bool:
+    return torch.is_tensor(index) and index.is_cuda
+
+
+def _as_torch_index(idx: torch.Tensor) -> torch.Tensor:
+    """An index tensor index_select / index_add_ accept (int32 or int64; a caller's CUDA index may be narrower)."""
+    return idx if idx.dtype in (torch.int32, torch.int64) else idx.long()
+
+
+def device_pair_index(index, name: str, n: int, m: int, device) -> torch.Tensor:
+    """The pair table on `device`: a CUDA tensor as it is (unchecked), anything else checked and uploaded through the cache."""
+    if _is_device_index(index):
+        return index
+    return _pair_index_cache.get(check_pair_index(index, name, n, m), device)
+
+
+def gather_pairs(pool: torch.Tensor, index, name: str = "index") -> torch.Tensor:
+    """The gathered route: pool[index] along dimension 0 (`pool` as it is for a None index).  Differentiable torch op."""
+    if index is None:
+        return pool
+    idx = device_pair_index(index, name, len(index), pool.shape[0], pool.device)
+    return pool.index_select(0, _as_torch_index(idx))
+
+
+def _pair_indices(spec: LayerSpec, ref, src, cam, ref_index, src_index, form: str):
+    """What forward_nhwc / forward_fused_nhwc / backward_nhwc do with their index arguments, first of all: the host checks
+    (ValueError, before anything touches the device), then the route.  Returns (ref, src, ref_index, src_index): the pools with
+    the device copies of the indices (indexed kernels), or the gathered maps with (None, None)."""
+    if ref_index is None and src_index is None:
+        return ref, src, None, None
+    n = cam.shape[0]
+    for t, nm in ((ref, "feat_ref"), (src, "feat_src")):
+        if not torch.is_tensor(t) or t.dim() != 4:
+            raise ValueError("%s must be a contiguous (M,H,W,C) pool of maps" % nm)
+    host = [None if idx is None or _is_device_index(idx) else check_pair_index(idx, nm, n, pool.shape[0])
+            for idx, nm, pool in ((ref_index, "ref_index", ref), (src_index, "src_index", src))]
+    _require_gpu(ref, "feat_ref")
+    _require_gpu(src, "feat_src")
+    dev = [idx if idx is None or _is_device_index(idx) else _pair_index_cache.get(h, ref.device)
+           for idx, h in zip((ref_index, src_index), host)]
+    if _is_device_index(ref_index) or _is_device_index(src_index) or not pair_index_applies(spec, ref.shape[-1], form):
+        take = lambda pool, idx: pool if idx is None else pool.index_select(0, _as_torch_index(idx))
+        return take(ref, dev[0]), take(src, dev[1]), None, None
+    return ref, src, dev[0], dev[1]
+
+
+def _ix_args(ref, src, ref_index, src_index):
+    """The four trailing arguments of an *_ix entry point."""
+    return _ptr(ref_index), _ptr(src_index), int(ref.shape[0]), int(src.shape[0])
+
+
 def forward_nhwc(spec: LayerSpec, ref: torch.Tensor, src: torch.Tensor, cam: torch.Tensor,
-                 want_attn=True, want_corr=True, res_bias=None, want_res_base=False, workspace=None):
+                 want_attn=True, want_corr=True, res_bias=None, want_res_base=False, workspace=None,
+                 ref_index=None, src_index=None):
     """ref/src: (N,H,W,C) contiguous.  Returns out (N,H,W,C), attn (N,K,H,W)|None, corr_pos (N,H,W,2)|None
     [, res_base (N,H,W,C) = ref + res_bias when want_res_base].  `workspace`: a caller-owned uint8 tensor for the
-    tile path (see tile_workspace / tile_stats) instead of the cached per-(device, stream) one."""
-    n, h, w, c = _require_pair(spec, ref, src, cam)
+    tile path (see tile_workspace / tile_stats) instead of the cached per-(device, stream) one.
+    `ref_index` / `src_index` (CPU integer tensors or sequences of N = cam.shape[0] values, each optional): ref / src are then
+    POOLS (M,H,W,C) and pair n reads ref[ref_index[n]], src[src_index[n]] -- in place (et_epipolar_forward_tiled_ix) where
+    pair_index_applies, from torch-gathered copies otherwise; the outputs stay per pair."""
+    ref, src, ref_index, src_index = _pair_indices(spec, ref, src, cam, ref_index, src_index, "forward")
+    n, h, w, c = _require_pair(spec, ref, src, cam, ref_index=ref_index, src_index=src_index)
     if res_bias is not None:
         if not want_res_base:
             raise ValueError("res_bias is added into res_base: it needs want_res_base")
         _require_vector(res_bias, "res_bias", c, ref.device)
     xs, ys, steps = spec.constants(ref.device)
-    out = _empty(None, like=ref)
+    out = _empty((n, h, w, c), device=ref.device)
     attn = _empty((n, spec.K, h, w), device=ref.device) if want_attn else None
     corr = _empty((n, h, w, 2), device=ref.device) if want_corr else None
-    base = _empty(None, like=ref) if want_res_base else None
+    base = _empty((n, h, w, c), device=ref.device) if want_res_base else None
     d = spec.desc(n, c)
     # variant 0 (the library default) takes the MFMA tile formulation wherever it applies (C == 256 head);
     # any explicit variant bit selects the per-pixel kernels
@@ -339,7 +476,11 @@ def forward_nhwc(spec: LayerSpec, ref: torch.Tensor, src: torch.Tensor, cam: tor
         ws = workspace if workspace is not None else _workspace(ref.device, ws_bytes, "fwd")
         _require_bytes(ws, "workspace", ws_bytes, ref.device,
                        "workspace of %d bytes on %s: need %d on %s" % (ws.numel(), ws.device, ws_bytes, ref.device))
-        _call("et_epipolar_forward_tiled", ref, *args, _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(ref))
+        if ref_index is not None or src_index is not None:
+            _call("et_epipolar_forward_tiled_ix", ref, *args, _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(ref),
+                  *_ix_args(ref, src, ref_index, src_index))
+        else:
+            _call("et_epipolar_forward_tiled", ref, *args, _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(ref))
         if POISON_OUTPUTS:          # (test suite: surface a device-side fault at the call that caused it)
             check_tile_errors(workspace=ws)
     else:
@@ -361,10 +502,13 @@ def fused_layer_applies(spec: LayerSpec, c: int, n: int = 1) -> bool:
 
 
 def forward_fused_nhwc(spec: LayerSpec, ref: torch.Tensor, src: torch.Tensor, cam: torch.Tensor, packed: torch.Tensor,
-                       bias: torch.Tensor, want_attn=True, want_corr=True, want_out=False, workspace=None):
+                       bias: torch.Tensor, want_attn=True, want_corr=True, want_out=False, workspace=None,
+                       ref_index=None, src_index=None):
     """The eval-mode layer as one data kernel (et_epipolar_forward_fused): returns x = ref + bias + out @ Wf^T (N,H,W,C),
-    attn (N,K,H,W)|None, corr_pos (N,H,W,2)|None [, out when want_out].  `packed`: residual_gemm_pack(Wf)."""
-    n, h, w, c = _require_pair(spec, ref, src, cam, c=256)
+    attn (N,K,H,W)|None, corr_pos (N,H,W,2)|None [, out when want_out].  `packed`: residual_gemm_pack(Wf).
+    `ref_index` / `src_index`: as forward_nhwc's (et_epipolar_forward_fused_ix: the ref row of x through ref_index)."""
+    ref, src, ref_index, src_index = _pair_indices(spec, ref, src, cam, ref_index, src_index, "fused")
+    n, h, w, c = _require_pair(spec, ref, src, cam, c=256, ref_index=ref_index, src_index=src_index)
     lib = _lib.load()
     need = int(lib.et_residual_gemm_packed_bytes())
     _require_bytes(packed, "packed", need, ref.device, "packed holds %d bytes on %s: the kernel reads %d on %s (ops.residual_gemm_pack)" %
@@ -373,19 +517,21 @@ def forward_fused_nhwc(spec: LayerSpec, ref: torch.Tensor, src: torch.Tensor, ca
     if workspace is not None:
         _require_bytes(workspace, "workspace", 0, ref.device, "workspace must be a uint8 tensor on %s" % (ref.device,))
     xs, ys, steps = spec.constants(ref.device)
-    x = _empty(None, like=ref)
+    x = _empty((n, h, w, c), device=ref.device)
     # `out`: requested -> a fresh tensor; otherwise scratch for the rows of overflow tiles only (normally none is written),
     # one buffer per (device, stream) like the workspace: all use is stream-ordered
-    out = _empty(None, like=ref) if want_out else _workspace(ref.device, ref.numel() * 4, "fwd_out_scratch").view(torch.float32)[:ref.numel()]
+    out = _empty((n, h, w, c), device=ref.device) if want_out else _workspace(ref.device, x.numel() * 4, "fwd_out_scratch").view(torch.float32)[:x.numel()]
     attn = _empty((n, spec.K, h, w), device=ref.device) if want_attn else None
     corr = _empty((n, h, w, 2), device=ref.device) if want_corr else None
     d = spec.desc(n, c)
     ws_bytes = int(lib.et_epipolar_forward_workspace_bytes(ctypes.byref(d)))
     with torch.cuda.device(ref.device):             # (held here: the poll asks about the CURRENT device's stream)
         ws = workspace if workspace is not None else _workspace(ref.device, max(ws_bytes, 1), "fwd")
-        _call("et_epipolar_forward_fused", None, ctypes.byref(d), _ptr(xs), _ptr(ys), _ptr(steps), _ptr(cam), _ptr(ref), _ptr(src),
-              _ptr(packed), _ptr(bias), _ptr(x), _ptr(attn), _ptr(corr), _ptr(out), 1 if want_out else 0, _ptr(ws),
-              ctypes.c_size_t(ws.numel()), _stream(ref))
+        indexed = ref_index is not None or src_index is not None
+        _call("et_epipolar_forward_fused_ix" if indexed else "et_epipolar_forward_fused", None, ctypes.byref(d), _ptr(xs), _ptr(ys),
+              _ptr(steps), _ptr(cam), _ptr(ref), _ptr(src), _ptr(packed), _ptr(bias), _ptr(x), _ptr(attn), _ptr(corr), _ptr(out),
+              1 if want_out else 0, _ptr(ws), ctypes.c_size_t(ws.numel()), _stream(ref),
+              *(_ix_args(ref, src, ref_index, src_index) if indexed else ()))
         if POISON_OUTPUTS:
             check_tile_errors(workspace=ws)
         else:
@@ -594,7 +740,7 @@ def _default_backward_form(spec: LayerSpec, tile_bytes: int, use_workspace: bool
 
 
 def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, form=None, attn=None, workspace=None,
-                  grad_attn=None):
+                  grad_attn=None, ref_index=None, src_index=None):
     """d(feat_ref), d(feat_src) of forward_nhwc.  Four forms of the same gradient:
       "tile"    MFMA tile formulation, d(feat_src) accumulated with float atomics across tiles: fastest,
                 reproducible to rounding only (C == 256, K <= 256);
@@ -610,16 +756,31 @@ def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, 
     `workspace`: a caller-owned uint8 tensor for the "tile" / "gather" form instead of the cached one (the tile form's has
     the forward's layout and size: tile_workspace).
     `grad_attn`: d loss / d attn (N,K,H,W) or None -- the gradient through the returned attention, in every form (the *_ga
-    entry points: e_k + ga_k in place of e_k = grad_out . S_k in the soft-max gradient)."""
-    n, h, w, c = _require_pair(spec, ref, src, cam)
+    entry points: e_k + ga_k in place of e_k = grad_out . S_k in the soft-max gradient).
+    `ref_index` / `src_index`: as forward_nhwc's -- ref / src are pools.  The return is then (d ref PER PAIR (N,H,W,C), d src over
+    the source POOL (M_src,H,W,C)): the "tile" form adds pair n's rows into map src_index[n] itself
+    (et_epipolar_backward_tiled_ix); every other form runs on gathered maps and torch's index_add_ reduces its d(src)."""
+    if ref_index is not None or src_index is not None:
+        if form is None:        # (the choice backward_nhwc would make for these maps, gathered: it does not depend on N)
+            d1 = spec.desc(1, int(ref.shape[-1]))
+            form = _default_backward_form(spec, int(_lib.load().et_epipolar_backward_tiled_workspace_bytes(ctypes.byref(d1))),
+                                          use_workspace)
+        pool_src, given_src = src, src_index
+        ref, src, ref_index, src_index = _pair_indices(spec, ref, src, cam, ref_index, src_index, form)
+        if given_src is not None and src_index is None:
+            # the gathered route: today's call on the pairs' copies, d(src) reduced into the pool
+            g_ref, g_pairs = backward_nhwc(spec, ref, src, cam, grad_out, use_workspace, form, attn, workspace, grad_attn)
+            idx = device_pair_index(given_src, "src_index", cam.shape[0], pool_src.shape[0], pool_src.device)
+            return g_ref, torch.zeros_like(pool_src).index_add_(0, _as_torch_index(idx), g_pairs)
+    n, h, w, c = _require_pair(spec, ref, src, cam, ref_index=ref_index, src_index=src_index)
     _require_gpu(grad_out, "grad_out")
-    if grad_out.shape != ref.shape or grad_out.device != ref.device:
+    if tuple(grad_out.shape) != (n, h, w, c) or grad_out.device != ref.device:
         raise ValueError("grad_out must be a float32 %s tensor on %s, got %s on %s" %
-                         (tuple(ref.shape), ref.device, tuple(grad_out.shape), grad_out.device))
+                         ((n, h, w, c), ref.device, tuple(grad_out.shape), grad_out.device))
     xs, ys, steps = spec.constants(ref.device)
     grad_out = grad_out.contiguous()
     grad_attn = _require_grad_attn(grad_attn, (n, spec.K, h, w), ref.device)
-    g_ref = _empty(None, like=ref)
+    g_ref = _empty((n, h, w, c), device=ref.device)
     g_src = _empty(None, like=src)
     d = spec.desc(n, c)
     lib = _lib.load()
@@ -640,6 +801,10 @@ def backward_nhwc(spec: LayerSpec, ref, src, cam, grad_out, use_workspace=True, 
         if attn is not None:
             _require_f32(attn, "attn", ref.device, (n, spec.K, h, w))
         # (the attention form of the float tile backward is handed the bytes it asked for, the deterministic form all it may use)
+        if ref_index is not None or src_index is not None:      # (form "tile": _pair_indices keeps an index for no other)
+            _call("et_epipolar_backward_tiled_ix", ref, *args[:7], _ptr(attn), *args[7:], _ptr(ws), ctypes.c_size_t(tile_bytes),
+                  _stream(ref), *_ix_args(ref, src, ref_index, src_index))
+            return g_ref, g_src
         _call("et_epipolar_backward_tiled_det_ga" if det else "et_epipolar_backward_tiled_ga", ref, *args[:7], _ptr(attn), *args[7:],
               _ptr(ws), ctypes.c_size_t(ws.numel() if det else tile_bytes), _stream(ref))
         if det and POISON_OUTPUTS:          # (test suite: the guard bit surfaces at the call that set it)
@@ -1291,3 +1456,39 @@ class EpipolarAttend(torch.autograd.Function):
         need_ref, need_src = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         return (g_ref.permute(0, 3, 1, 2) if need_ref else None,
                 g_src.permute(0, 3, 1, 2) if need_src else None, None, None, None)
+
+
+class EpipolarAttendIndexed(torch.autograd.Function):
+    """EpipolarAttend with the pairs named by index into stacks of maps (ET_HAS_PAIR_INDEX): `pool_ref` (M_ref,C,H,W) and
+    `pool_src` (M_src,C,H,W), logical NCHW -- they may be ONE tensor --, `cam` (N,27), and `ref_index` / `src_index` as
+    forward_nhwc takes them (None: that operand holds one map per pair).  Pair n attends pool_ref[ref_index[n]] to
+    pool_src[src_index[n]]; out (N,C,H,W), attn and corr_pos are per pair.  What autograd keeps are the POOLS, never gathered
+    copies; d(pool_src) comes straight from the tile kernel (pair n's rows added into map src_index[n]), d(pool_ref) is the
+    per-pair d(feat_ref) reduced with index_add_ (with a None ref_index: the kernel's tensor itself); when both pools are one
+    tensor autograd sums the two.  Shapes and specs the indexed kernels do not take (pair_index_applies) run on torch-gathered
+    maps inside the same calls, with the same results."""
+
+    @staticmethod
+    def forward(ctx, pool_ref, pool_src, cam, spec: LayerSpec, ref_index=None, src_index=None, attn_grad: bool = False):
+        ref = to_nhwc(pool_ref)
+        src = ref if pool_src is pool_ref else to_nhwc(pool_src)
+        out, attn, corr = forward_nhwc(spec, ref, src, cam, ref_index=ref_index, src_index=src_index)
+        ctx.spec, ctx.index = spec, (ref_index, src_index)
+        ctx.save_for_backward(ref, src, cam, attn)
+        _mark_attention(ctx, attn, corr, attn_grad)
+        return out.permute(0, 3, 1, 2), attn, corr
+
+    @staticmethod
+    def backward(ctx, grad_out, grad_attn, _gc):
+        ref, src, cam, attn = ctx.saved_tensors
+        ref_index, src_index = ctx.index
+        n = cam.shape[0]
+        g = (torch.zeros((n,) + tuple(ref.shape[1:]), device=ref.device) if grad_out is None else to_nhwc(grad_out))
+        g_ref, g_src = backward_nhwc(ctx.spec, ref, src, cam, g, attn=attn, grad_attn=grad_attn if ctx.attn_grad else None,
+                                     ref_index=ref_index, src_index=src_index)
+        need_ref, need_src = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if need_ref and ref_index is not None:
+            idx = device_pair_index(ref_index, "ref_index", n, ref.shape[0], ref.device)
+            g_ref = torch.zeros_like(ref).index_add_(0, _as_torch_index(idx), g_ref)
+        return (g_ref.permute(0, 3, 1, 2) if need_ref else None,
+                g_src.permute(0, 3, 1, 2) if need_src else None, None, None, None, None, None)

@@ -33,6 +33,8 @@ extern "C" {
 /* The *_ga entry points (gradient through the returned attention) were added without touching an existing signature, so the
  * version stays; a caller tests for them with this macro. */
 #define ET_HAS_ATTN_GRAD 1
+/* The *_ix entry points (pairs named by index into a stack of maps, below et_epipolar_forward_fused) were added the same way. */
+#define ET_HAS_PAIR_INDEX 1
 
 /* Static description of one layer call: the cfg keys the reference reads in
  * Epipolar.__init__ (epipolar.py:12-54) and at call time (epipolar.py:303-311,
@@ -441,6 +443,42 @@ int et_epipolar_forward_fused(const EtLayerDesc *desc, const float *xs, const fl
                               const float *cam, const float *feat_ref, const float *feat_src, const void *packed_w,
                               const float *bias, float *x, float *attn, float *corr_pos, float *out_scratch,
                               int32_t want_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Pairs named by index into a stack of maps (ET_HAS_PAIR_INDEX).  A backbone runs once per view and returns ONE stack of maps;
+ * the entry points above address their maps as base + n * H*W*C, so a caller had to gather a private copy of both maps of every
+ * pair first.  The *_ix forms of the tile family take two POOLS instead,
+ *   feat_ref : (M_ref,H,W,256)    feat_src : (M_src,H,W,256)        (they may be the same memory)
+ *   ref_index, src_index : (N) int32 DEVICE arrays, each nullable
+ * and pair n reads feat_ref[ref_index[n]] and feat_src[src_index[n]].  Every other array -- cam, out, x, attn, corr_pos, res_base,
+ * out_scratch, grad_out, grad_attn, grad_ref, the workspace -- stays per pair, N of each, and every other argument is its unindexed
+ * sibling's.  A NULL index is the identity (its pool then holds exactly N maps, M == N, else an error); with both NULL a call is
+ * its sibling's, bit for bit: the siblings ARE these functions with NULL indices.
+ *   et_epipolar_forward_tiled_ix  : et_epipolar_forward_tiled
+ *   et_epipolar_forward_fused_ix  : et_epipolar_forward_fused (the feat_ref row of x = feat_ref + bias + out . Wf^T through ref_index)
+ *   et_epipolar_backward_tiled_ix : et_epipolar_backward_tiled_ga (float atomics; attn and grad_attn nullable).
+ *       grad_src : (M_src,H,W,256), the gradient of the source POOL: all M_src maps are cleared, pair n's rows are added into map
+ *                  src_index[n] (several pairs may name one map; a map no pair names comes back 0).
+ *       grad_ref : (N,H,W,256), per pair as before: the caller adds pair n's map into pool map ref_index[n].
+ * The index values must lie in [0, M): the caller checks them (the Python binding does, on the host).  The kernels clamp what they
+ * read into that range, so a bad index gives a wrong answer but never an access outside the pools.
+ * Not indexed: the deterministic tile backward (its quantum and int64 accumulator are per pair), the per-pixel forward, the gather
+ * and atomic per-pixel backward, the general kernels, and every shape the tile path does not take (C != 256): gather the pairs'
+ * maps and call the unindexed entry points there. */
+int et_epipolar_forward_tiled_ix(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                                 const float *cam, const float *feat_ref, const float *feat_src, float *out,
+                                 float *attn, float *corr_pos, const float *res_bias, float *res_base,
+                                 void *workspace, size_t workspace_bytes, void *stream, const int32_t *ref_index,
+                                 const int32_t *src_index, int32_t M_ref, int32_t M_src);
+int et_epipolar_forward_fused_ix(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                                 const float *cam, const float *feat_ref, const float *feat_src, const void *packed_w,
+                                 const float *bias, float *x, float *attn, float *corr_pos, float *out_scratch,
+                                 int32_t want_out, void *workspace, size_t workspace_bytes, void *stream,
+                                 const int32_t *ref_index, const int32_t *src_index, int32_t M_ref, int32_t M_src);
+int et_epipolar_backward_tiled_ix(const EtLayerDesc *desc, const float *xs, const float *ys, const float *steps,
+                                  const float *cam, const float *feat_ref, const float *feat_src, const float *attn,
+                                  const float *grad_out, const float *grad_attn, float *grad_ref, float *grad_src,
+                                  void *workspace, size_t workspace_bytes, void *stream, const int32_t *ref_index,
+                                  const int32_t *src_index, int32_t M_ref, int32_t M_src);
 
 /* Peak finder of the pose head: find_tensor_peak_batch (modeling/backbones/basic_batch.py:17-63), which
  * PoseResNet.forward calls once per sample in a Python loop (resnet.py:424-430).  One launch for all maps.
