@@ -26,6 +26,7 @@ ET_VARIANT_BWD_SPLIT_IN_PLACE = 2097152
 ET_VARIANT_BWD_DETERMINISTIC = 4194304
 ET_ABI_VERSION = 14
 ET_HAS_PAIR_INDEX = 1
+ET_HAS_META_FUSION = 1
 ET_GENERAL_POOLING = 1
 ET_GENERAL_PRIOR_MUL = 2
 ET_GENERAL_COSINE = 4
@@ -95,6 +96,11 @@ _SIGNATURES = {
     "et_z_batch_stats": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "et_z_wgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "et_z_wgrad": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    # ET_HAS_META_FUSION: the Meta fusion layer's per-pair GEMMs
+    "et_meta_pack": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int32, _P, _P]),
+    "et_meta_gemm": (ctypes.c_int, [ctypes.c_int32] * 3 + [_P] * 6),
+    "et_meta_wgrad_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
+    "et_meta_wgrad": (ctypes.c_int, [ctypes.c_int32] * 3 + [_P] * 5 + [ctypes.c_size_t, _P]),
     "et_z_backward_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
     "et_z_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, _P, _P, _P, _P, _P, _P, ctypes.c_int32, _P, _P, _P, _P, _P,
                                      ctypes.c_size_t, _P]),

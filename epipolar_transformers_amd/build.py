@@ -29,6 +29,7 @@ UNITS = {
                              "et_tile_host.h", "et_tile_layout.h", "et_wave_reduce.h", "et_split_f16.h", "et_lds_layout.h"],
     "et_misc.hip": ["kernels_misc.inc", "et_peaks.h"],
     "et_residual_gemm.hip": ["kernels_residual_gemm.inc", "et_wave_reduce.h"],
+    "et_meta.hip": ["kernels_meta.inc", "kernels_residual_gemm.inc", "et_wave_reduce.h"],
     "et_triangulate.hip": ["et_triangulate.h", "et_wave_reduce.h"],
     "et_rpsm.hip": ["et_rpsm.h"],
     "et_metrics.hip": ["et_metrics.h", "et_wave_reduce.h"],

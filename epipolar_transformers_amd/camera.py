@@ -108,6 +108,36 @@ def pair_algebra(P_ref: torch.Tensor, P_src: torch.Tensor) -> torch.Tensor:
     return torch.cat([p1inv.reshape(n, 12), P2.reshape(n, 12), e2.reshape(n, 3)], 1).contiguous()
 
 
+def fundamental_matrices(P_ref: torch.Tensor, P_src: torch.Tensor) -> torch.Tensor:
+    """(N,3,4),(N,3,4) -> (N,3,3) float32 CPU tensor F = [P2 C1]x (P2 pinverse(P1)): `findFundamentalMat(P1, P2, engine='torch')`
+    (vision/multiview.py:85-124) without its prints -- the embedding of the Meta fusion layer (modeling/layers/meta.py:35).
+
+    The same torch ops in the same order on the host, for the reason `pair_algebra` gives (cond(P) ~ 1e6): the loop of
+    `pinverse()` through `batched_pinverse`, the centre C1 through `torch.inverse` as `camera_center` forms it (:16-21, NOT divided by
+    its last coordinate, which is 1 by construction).  The entries are of the order of the pixel-scale epipole times P2 pinverse(P1):
+    1e5 - 1e6 for the usual rigs."""
+    P1 = P_ref.detach().to("cpu", torch.float32)
+    P2 = P_src.detach().to("cpu", torch.float32)
+    if P1.dim() != 3 or P1.shape[1:] != (3, 4) or P2.shape != P1.shape:
+        raise ValueError("expected two (N,3,4) projection-matrix batches, got %s and %s"
+                         % (tuple(P_ref.shape), tuple(P_src.shape)))
+    n = P1.shape[0]
+    p2p1inv = torch.matmul(P2, batched_pinverse(P1))                 # multiview.py:101-105
+    inv_a = torch.inverse(P1[..., :3])                               # multiview.py:17
+    centre = -torch.matmul(inv_a, P1[..., 3, None])                  # multiview.py:18
+    hom = torch.ones([n, 4, 1], dtype=torch.float32)                 # multiview.py:19-20
+    hom[..., :3, :] = centre
+    e2 = torch.matmul(P2, hom).view(n, 3)                            # multiview.py:114
+    cross = torch.zeros_like(p2p1inv)                                # multiview.py:116-122
+    cross[..., 0, 1] = -e2[..., 2]
+    cross[..., 0, 2] = e2[..., 1]
+    cross[..., 1, 2] = -e2[..., 0]
+    cross[..., 1, 0] = e2[..., 2]
+    cross[..., 2, 0] = -e2[..., 1]
+    cross[..., 2, 1] = e2[..., 0]
+    return torch.matmul(cross, p2p1inv).contiguous()                 # multiview.py:123
+
+
 class PairAlgebraCache:
     """Small value-keyed cache (camera rigs repeat across frames and steps).
     Keyed on the BYTES of the matrices, never on tensor identity: a data loader frees and re-allocates its batches,
@@ -120,8 +150,9 @@ class PairAlgebraCache:
     inverse), the reference's CPU path; a reference running pinverse on a GPU can differ in the last bits, and the
     layer is discontinuous in them."""
 
-    def __init__(self, max_entries: int = 8):
+    def __init__(self, max_entries: int = 8, algebra=pair_algebra):
         self.max_entries = max_entries
+        self.algebra = algebra          # the host function cached: pair_algebra, or fundamental_matrices for the Meta layer
         self._store = {}
 
     def get(self, P_ref: torch.Tensor, P_src: torch.Tensor, device, host=None) -> torch.Tensor:
@@ -131,7 +162,7 @@ class PairAlgebraCache:
         key = (a.numpy().tobytes(), b.numpy().tobytes(), str(device))
         hit = self._store.get(key)
         if hit is None:
-            cam = pair_algebra(a, b)
+            cam = self.algebra(a, b)
             if torch.device(device).type == "cuda":
                 cam = cam.pin_memory().to(device, non_blocking=True)
             if len(self._store) >= self.max_entries:

@@ -211,6 +211,9 @@ def default_cfg() -> CfgNode:
                                               # name every (reference, source) pair by index into it -- the tile kernels read the
                                               # maps in place (ET_HAS_PAIR_INDEX) instead of from torch-gathered per-pair copies;
                                               # same results (ops.pair_index_applies: where the gather remains)
+    C.EPIPOLAR_AMD.META_FUSION = False        # True: the registry names metaHG / metaHG1 / metaHG11 build the Meta fusion layer
+                                              # (meta.Meta: a 256 x 256 weight per pair from its fundamental matrix, applied by the
+                                              # per-pair HIP GEMMs et_meta_*), metaepipolarHG* what epipolarHG* builds; False: they raise
     C.EPIPOLAR_AMD.TRUNK_DTYPE = "fp32"       # arithmetic of the stock trunk (convolutions of `PoseResNet.trunk`): fp32 (the reference's)
                                               # | bf16 | fp16 = torch.autocast around it; the epipolar layer stays fp32 either way
     return C

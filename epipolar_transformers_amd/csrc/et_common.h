@@ -22,6 +22,8 @@
 //                                                    kernels' LDS layouts (plain constexpr C++, also built by a host test)
 //   et_residual_gemm.hip  kernels_residual_gemm.inc  x = feat + bias + out . Wf^T as a split-fp16 GEMM, and the z branch's
 //                                                    batch statistics / backward (et_residual_gemm, et_z_*)
+//   et_meta.hip           kernels_meta.inc           the Meta fusion layer: the same GEMM with a weight per pair, its pack and its
+//                                                    per-pair weight gradient (et_meta_pack / _gemm / _wgrad)
 //   et_triangulate.hip    et_triangulate.h           KEYPOINT.TRIANGULATION epipolar / epipolar_dlt: one wave per (frame, joint), a
 //                                                    lane per hypothesis, float64 Givens + Jacobi SVD; host + device routine.
 //                                                    pymvg / naive / refine (et_triangulate_views): a lane per joint / the same

@@ -1,5 +1,5 @@
 """The stacked-hourglass callers of the epipolar layer: registry names `HG*` / `epipolarHG*` /
-`simplemultiviewHG*`, one call of the operator per hourglass stack (two with MERGE both).
+`simplemultiviewHG*` / `metaHG*` / `metaepipolarHG*`, one call of the operator per hourglass stack (two with MERGE both).
 
 Reference surface (modeling/backbones/ProHG.py):
   * factories `hourglass` / `hourglass1` / `hourglass11`                        :326-395  (3 stacks x depth 3, 1 x 3, 1 x 1;
@@ -13,8 +13,14 @@ Reference surface (modeling/backbones/ProHG.py):
     `conv_A|B|C.{0,2}`, `branch.{0,2}`, inside an hourglass `res.<n>`, `down.<1+n>`, `mid...`, `up.<n>`).
 
 The convolutions are stock PyTorch-ROCm (MIOpen); the fusion is the HIP operator (`epipolar.Epipolar`: with the default 256
-features the MFMA tile kernels, eval mode through the one-kernel layer).  Not built: the `meta*` variants (modeling/layers/meta.py is
-outside the path) and EPIPOLAR.WARPEDHEATMAP (a visualisation aid, :301-304) -- both raise.
+features the MFMA tile kernels, eval mode through the one-kernel layer).
+
+The `meta*` names sit behind EPIPOLAR_AMD.META_FUSION (default False: the constructor raises for all of them).  With the knob,
+`metaHG*` fuses through the Meta layer (`meta.Meta`, modeling/layers/meta.py: a weight per pair from its fundamental matrix, applied by
+the per-pair HIP GEMMs of `ops.meta_fuse` with `ret + feat` in the same pass) -- `self.meta`, one per stack, and `self.testmeta`, unused
+in forward but in the reference's state dict (:183-188) -- and `metaepipolarHG*` builds what `epipolarHG*` builds: in the reference
+`'metaHG' in 'metaepipolarHG'` is false and `'epipolarHG' in` it is true.  Not built: EPIPOLAR.WARPEDHEATMAP (a visualisation aid,
+:301-304), which raises.
 """
 from __future__ import annotations
 
@@ -23,8 +29,9 @@ from torch import nn
 import torch.nn.functional as F
 
 from .backbones import BACKBONES, find_peaks, peak_grad
-from .config import get_cfg
+from .config import amd_knob, get_cfg
 from .epipolar import Epipolar
+from .meta import Meta
 
 
 def _bn_relu_conv(cin, cout, k):
@@ -76,7 +83,7 @@ class HourGlassPoseNet(nn.Module):
         super().__init__()
         self.cfg = cfg
         body = cfg.BACKBONE.BODY
-        if "meta" in body:
+        if "meta" in body and not amd_knob(cfg, "META_FUSION", False):
             raise NotImplementedError("%s: the Meta fusion layer (modeling/layers/meta.py) is outside this package's path" % body)
         feats, joints = cfg.KEYPOINT.NFEATS, cfg.KEYPOINT.NUM_PTS
         self.nStack, self.sigma, self.downsample = stacks, cfg.KEYPOINT.SIGMA, 4
@@ -94,7 +101,10 @@ class HourGlassPoseNet(nn.Module):
         self.trsfeas = nn.ModuleList(nn.Conv2d(feats, feats, kernel_size=1, bias=True) for _ in range(stacks - 1))
         self.trstmps = nn.ModuleList(nn.Conv2d(joints, feats, kernel_size=1, bias=True) for _ in range(stacks - 1))
         self.sigmoid = None                                                  # (every factory of the reference: "sigmoid": 0)
-        if "epipolarHG" in body:
+        if "metaHG" in body:                                                 # ProHG.py:183-188
+            self.meta = nn.ModuleList(Meta(feats) for _ in range(stacks))
+            self.testmeta = Meta(feats)
+        elif "epipolarHG" in body:
             self.epipolar_sampler = Epipolar(cfg=cfg)
         self.avgpool = nn.AvgPool2d(kernel_size=4)
 
@@ -109,6 +119,8 @@ class HourGlassPoseNet(nn.Module):
         corr_pos = depth = sample_locs = None
         if "simplemultiviewHG" in body:
             ret = other_features[i]
+        elif "metaHG" in body:                                                # :219-220, `ret + feat` in the layer's one pass
+            return self.meta[i](KRT, other_KRT, other_features[i], feat=None if e.OTHER_ONLY else feat), None, None, None
         elif "epipolarHG" in body:
             if e.FIND_CORR == "rgb":                                          # :218-228: 4 x 4 average-pooled images as the
                 assert not e.PRIOR                                            # correspondence maps
@@ -192,5 +204,5 @@ def _factory(stacks, depth):
 
 
 for _suffix, (_stacks, _depth) in (("", (3, 3)), ("1", (1, 3)), ("11", (1, 1))):          # ProHG.py:319-395
-    for _prefix in ("HG", "simplemultiviewHG", "epipolarHG", "metaHG", "metaepipolarHG"):   # (meta*: the constructor raises)
+    for _prefix in ("HG", "simplemultiviewHG", "epipolarHG", "metaHG", "metaepipolarHG"):   # (meta*: EPIPOLAR_AMD.META_FUSION)
         BACKBONES.register(_prefix + _suffix, _factory(_stacks, _depth))

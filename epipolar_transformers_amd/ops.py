@@ -964,6 +964,102 @@ def z_wgrad(grad_y: torch.Tensor, out: torch.Tensor, workspace: torch.Tensor = N
     return gw, gb
 
 
+def _require_meta_rows(t: torch.Tensor, name: str, device, shape=None):
+    """`t`: the channels-last rows of N pairs, (N, ..., 256) contiguous float32 -- of `shape` where one is given."""
+    _require_f32(t, name, device, (..., 256) if shape is None else shape,
+                 "%s must be a contiguous channels-last (N, ..., 256) float32 tensor%s on %s, got %s on %s" % (
+                     name, "" if shape is None else " of shape %s" % (tuple(shape),), device, tuple(t.shape), t.device))
+    if t.dim() < 3 or t.numel() == 0:
+        raise ValueError("%s must be (N, ..., 256) with N >= 1 pairs of at least one row, got %s" % (name, tuple(t.shape)))
+
+
+def meta_pack(weight: torch.Tensor, share: torch.Tensor = None, transpose: bool = False) -> torch.Tensor:
+    """Lay `weight[n] + share` (its transpose with `transpose`) out for `meta_gemm`, pair by pair (et_meta_pack): weight N x 65536
+    values -- (N, 256 out, 256 in) in any shape --, share 65536 values or None.  Returns the packed uint8 buffer,
+    et_residual_gemm_packed_bytes() bytes per pair; repack when the weights change."""
+    _require_f32(weight, "weight", weight.device)
+    n = weight.shape[0] if weight.dim() else 0
+    if n < 1 or weight.numel() != n * 65536:
+        raise ValueError("meta_pack is written for the 256-channel head: weight must hold N x 256 x 256 values, got %s" % (tuple(weight.shape),))
+    if share is not None:
+        _require_vector(share, "share", 65536, weight.device)
+    packed = torch.empty(n * int(_lib.load().et_residual_gemm_packed_bytes()), dtype=torch.uint8, device=weight.device)
+    _call("et_meta_pack", weight, n, 256, _ptr(weight), _ptr(share), 1 if transpose else 0, _ptr(packed), _stream(weight))
+    return packed
+
+
+def meta_gemm(src: torch.Tensor, packed: torch.Tensor, bias: torch.Tensor = None, feat: torch.Tensor = None) -> torch.Tensor:
+    """x[n] = [feat[n] +] [bias +] src[n] @ W_n^T over the rows of every pair n (et_meta_gemm): src (N, ..., 256) channels-last,
+    `packed` from `meta_pack` for the same N."""
+    _require_meta_rows(src, "src", src.device)
+    n, c = src.shape[0], src.shape[-1]
+    if feat is not None:
+        _require_meta_rows(feat, "feat", src.device, src.shape)
+    if bias is not None:
+        _require_vector(bias, "bias", c, src.device)
+    _require_bytes(packed, "packed", n * int(_lib.load().et_residual_gemm_packed_bytes()), src.device,
+                   "packed must be the buffer meta_pack returns for these %d pairs" % n)
+    x = _empty(None, like=src)
+    _call("et_meta_gemm", src, n, src.numel() // (n * c), c, _ptr(src), _ptr(feat), _ptr(packed), _ptr(bias), _ptr(x), _stream(src))
+    return x
+
+
+def meta_wgrad(g: torch.Tensor, src: torch.Tensor, want_bias: bool = True, workspace: torch.Tensor = None):
+    """grad_w (N, 256, 256): grad_w[n] = g[n]^T @ src[n], and grad_b (256) = g summed over every row of every pair (None without
+    `want_bias`), from (N, ..., 256) channels-last tensors (et_meta_wgrad: three-term bf16 MFMAs, no atomics, bit-reproducible).
+    `workspace`: a caller-owned uint8 tensor instead of the cached one (any contents)."""
+    _require_meta_rows(g, "g", g.device)
+    _require_meta_rows(src, "src", g.device, g.shape)
+    n, c = g.shape[0], g.shape[-1]
+    hw = g.numel() // (n * c)
+    gw = _empty((n, c, c), device=g.device)
+    gb = _empty((c,), device=g.device) if want_bias else None
+    ws_bytes = int(_lib.load().et_meta_wgrad_workspace_bytes(n, hw))
+    ws = _own_workspace(workspace, ws_bytes, g.device, "metawgrad")
+    _call("et_meta_wgrad", g, n, hw, c, _ptr(g), _ptr(src), _ptr(gw), _ptr(gb), _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(g))
+    return gw, gb
+
+
+class MetaFuse(torch.autograd.Function):
+    """x = [feat +] share_bias + src . (weight + share_weight)^T per pair: one pack + one GEMM forward; backward a transposed pack +
+    the GEMM for d src, et_meta_wgrad for d weight (d share_weight is its sum over the pairs, d share_bias its row sum), d feat = g."""
+
+    @staticmethod
+    def forward(ctx, src, weight, share_weight, share_bias, feat):
+        ctx.save_for_backward(src, weight, share_weight)
+        ctx.has_bias = share_bias is not None
+        return meta_gemm(src, meta_pack(weight, share_weight), share_bias, feat)
+
+    @staticmethod
+    def backward(ctx, g):
+        src, weight, share_weight = ctx.saved_tensors
+        need_src, need_w, need_sw, need_b, need_feat = ctx.needs_input_grad
+        g = g.contiguous()
+        d_src = meta_gemm(g, meta_pack(weight, share_weight, transpose=True)) if need_src else None
+        d_w = d_sw = d_b = None
+        if need_w or need_sw or (need_b and ctx.has_bias):
+            gw, d_b = meta_wgrad(g, src, want_bias=need_b and ctx.has_bias)
+            d_w = gw.view_as(weight) if need_w else None
+            d_sw = gw.sum(0).view_as(share_weight) if need_sw else None
+        return d_src, d_w, d_sw, d_b, g if need_feat else None
+
+
+def meta_fuse(src: torch.Tensor, weight: torch.Tensor, share_weight: torch.Tensor, share_bias: torch.Tensor = None,
+              feat: torch.Tensor = None) -> torch.Tensor:
+    """The Meta fusion layer's data pass (modeling/layers/meta.py:42-50 and the hourglass caller's `ret + feat`) for the 256-channel
+    head, differentiable in every argument:
+        x[n, m, :] = [feat[n, m, :] +] [share_bias +] src[n, m, :] @ (weight[n] + share_weight)^T
+    src / feat: (N, ..., 256) channels-last contiguous; weight: N x 256 x 256 values (out, in); share_weight: 256 x 256 values (a
+    1x1 convolution's weight as it stands) or None; share_bias (256) or None."""
+    _require_meta_rows(src, "src", src.device)
+    weight = weight.contiguous()
+    if share_weight is not None:
+        share_weight = share_weight.contiguous()
+    if share_bias is not None:
+        share_bias = share_bias.contiguous()
+    return MetaFuse.apply(src, weight, share_weight, share_bias, feat)
+
+
 def _heatmap_peaks(hm: torch.Tensor, radius: float, downsample: float, threshold: float, legacy: int):
     n, j, h, w = hm.shape
     locs = _empty((n, j, 2), device=hm.device)

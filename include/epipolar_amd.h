@@ -35,6 +35,8 @@ extern "C" {
 #define ET_HAS_ATTN_GRAD 1
 /* The *_ix entry points (pairs named by index into a stack of maps, below et_epipolar_forward_fused) were added the same way. */
 #define ET_HAS_PAIR_INDEX 1
+/* The et_meta_* entry points (the Meta fusion layer's per-pair GEMMs, below et_z_wgrad) were added the same way. */
+#define ET_HAS_META_FUSION 1
 
 /* Static description of one layer call: the cfg keys the reference reads in
  * Epipolar.__init__ (epipolar.py:12-54) and at call time (epipolar.py:303-311,
@@ -423,6 +425,34 @@ int et_z_backward(int64_t num_pixels, int32_t C, const float *g, const float *y,
 size_t et_z_wgrad_workspace_bytes(int64_t num_pixels);
 int et_z_wgrad(int64_t num_pixels, int32_t C, const float *grad_y, const float *out, float *grad_w, float *grad_b, void *workspace,
                size_t workspace_bytes, void *stream);
+
+/* The Meta fusion layer (ET_HAS_META_FUSION; modeling/layers/meta.py:27-50 and the hourglass caller's `ret + feat`,
+ * ProHG.py:219-220,239) for the 256-channel head: every (reference, source) pair n applies a 256 x 256 weight of ITS OWN to its
+ * source map,
+ *     x[n, m, :] = [feat[n, m, :] +] [bias +] src[n, m, :] . W_n^T,      W_n = weight[n] + share,
+ * the reference's loop of N conv2d calls + shared 1x1 convolution + two adds as ONE pass over the maps.  Rows are channels-last:
+ * src / feat / x / g are (N, HW, 256) fp32 contiguous, weight / grad_w (N, 256 out, 256 in), share (256, 256).
+ *   et_meta_pack  : `weight[n] + share` (share nullable: weight[n] alone), or its TRANSPOSE when `transpose` != 0, split and laid
+ *                   out as et_residual_gemm_pack lays Wf out -- pair n at byte n * et_residual_gemm_packed_bytes() of `packed`
+ *                   (16-byte aligned), under a power-of-two scale from the largest magnitude of THAT pair's sum.
+ *   et_meta_gemm  : the product above on the split-fp16 MFMA scheme of et_residual_gemm (fp32-level error, every row of `src`
+ *                   under its own scale), B read from pair n's pack.  Tiles of 64 rows PER PAIR: ceil(HW / 64) tiles each, none
+ *                   spans two pairs, the rows of a pair's last tile at or beyond HW are neither loaded nor stored.  feat, bias
+ *                   nullable.  With the transposed packs and neither: d src[n] = g[n] . W_n.  x may not alias src or feat.
+ *   et_meta_wgrad : grad_w[n] = g[n]^T . src[n] per pair and grad_b (256, nullable) = the sum of g over ALL N HW rows: the
+ *                   three-term bf16 MFMA form of et_z_wgrad, a pair's rows split over ceil(HW / 2048) blocks (a number that depends
+ *                   on HW alone), partial results in `workspace` (et_meta_wgrad_workspace_bytes(N, HW) bytes, no initialisation
+ *                   needed) summed in a fixed order.  d share = sum_n grad_w[n] is left to the caller.
+ * No kernel uses atomics: the same inputs give the same bits, and pair n's rows of x / d src / grad_w are the same bits whether
+ * the pair is computed alone or inside any batch.  Non-finite: as et_residual_gemm (a non-finite row of src gives a non-finite
+ * row of x, every other row is computed as on finite inputs); a non-finite weight is packed as et_residual_gemm_pack packs one and
+ * reaches the rows of its own pair only. */
+int et_meta_pack(int32_t N, int32_t C, const float *weight, const float *share, int32_t transpose, void *packed, void *stream);
+int et_meta_gemm(int32_t N, int32_t HW, int32_t C, const float *src, const float *feat, const void *packed, const float *bias,
+                 float *x, void *stream);
+size_t et_meta_wgrad_workspace_bytes(int32_t N, int32_t HW);
+int et_meta_wgrad(int32_t N, int32_t HW, int32_t C, const float *g, const float *src, float *grad_w, float *grad_b, void *workspace,
+                  size_t workspace_bytes, void *stream);
 
 /* The whole eval-mode layer as ONE data kernel (ABI 11): the sampling + attention of et_epipolar_forward_tiled with
  *     x = feat_ref + bias + out . Wf^T
